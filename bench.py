@@ -28,7 +28,21 @@ random_crop 448 + hflip, u8) are the other device-resident configurations;
 224 f32: 11.8:1 and 15.6:1 downscales) measure large ratios.  DESIGN.md
 quotes them.
 
-Extra fields:
+A plain run does what the headline needs and no more: it sets up, warms up,
+times the steps, writes its outputs if `--dump-outputs DIR` is given and prints
+the result line (`roofline`, `workloads`, `cpu_baseline`, `e2e_jpeg` and `e2e`
+are null).  `--full` adds the extra fields below, each from runs of its own
+after the timed steps; `--no-cpu`, `--no-e2e`, `--no-e2e-jpeg`, `--no-copy`
+and `--no-others` drop single legs of a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step computed -- the output
+batch a caller of `mxd_resize_crop_batch` receives, NHWC -- as
+`DIR/output.npy` (`output_rank<r>.npy` for the other ranks of a multi-GPU
+run) in float32: the whole batch when it fits 64 MB, else the images of a
+fixed seeded sample of the batch, in batch order.  Inputs and geometry are
+seeded, so two builds run with the same arguments write comparable files.
+
+Extra fields (`--full`):
   roofline      HBM roofline of the fused kernel: algorithmic bytes per launch
                 (source footprint the kept window depends on + output bytes, per
                 image, summed over the batch) / average launch time from HIP
@@ -384,6 +398,25 @@ def launch_windows(capi, stream, launch, sync):
     return ks[len(ks) // 2], hs[len(hs) // 2], [round(v, 5) for v in (r[0] for r in runs)]
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, name, dst, geoms, f32, stream):
+    """--dump-outputs: the output batch in `dst` (NHWC, every image of a
+    workload has the same crop size) as out_dir/name.npy in float32.  A batch
+    over DUMP_MAX_BYTES is cut to a fixed seeded sample of its images, kept in
+    batch order.  Returns the path."""
+    B, cw, ch = len(geoms), geoms[0][4], geoms[0][5]
+    assert all((g[4], g[5]) == (cw, ch) for g in geoms)
+    k = max(1, min(B, DUMP_MAX_BYTES // (ch * cw * C * 4)))
+    idx = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    batch = dst.download((B, ch, cw, C), np.float32 if f32 else np.uint8, stream=stream)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, name + ".npy")
+    np.save(path, batch[idx].astype(np.float32, copy=False))
+    return path
+
+
 def marketing_name(arch):
     """The agent's "Marketing Name" from rocminfo (a child process), or None."""
     out = ""
@@ -405,15 +438,16 @@ def marketing_name(arch):
     return None
 
 
-def manifest(capi, dev):
-    """Run manifest: device, ROCm, host cores, decoder."""
+def manifest(capi, dev, full=True):
+    """Run manifest: device, ROCm, host cores, decoder.  The
+    marketing name costs a child process, so only a `--full` run asks for it."""
     m = {"host_cores": host_cores(), "jpeg": "native (libjpeg-turbo ISLOW semantics, mxd_jpeg_decode)"}
     try:
         name, arch, cus = capi.device_properties(dev)
         m.update(gpu=name, arch=arch, compute_units=cus)
     except Exception:  # noqa: BLE001  (a manifest never fails the bench)
         pass
-    m["gpu_marketing_name"] = marketing_name(m.get("arch", ""))
+    m["gpu_marketing_name"] = marketing_name(m.get("arch", "")) if full else None
     try:
         with open("/opt/rocm/.info/version") as f:
             m["rocm"] = f.read().strip()
@@ -479,6 +513,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (default: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the extra fields (roofline, workloads, cpu_baseline, "
+                         "e2e, e2e_jpeg); the --no-* options drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output batch to DIR/output.npy (float32, at most 64 MB)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-e2e-jpeg", action="store_true")
@@ -505,6 +544,9 @@ def main():
     # e2e_jpeg's 16-queue leg (a child process of the default run)
     ap.add_argument("--e2e-jpeg-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs and (args.split_devices > 1 or args.simulate > 0):
+        ap.error("--dump-outputs writes the batch of the one-device-per-process path: not with --split-devices "
+                 "or --simulate")
     if args.e2e_jpeg_child:
         from mlx_data_amd import capi
 
@@ -605,6 +647,28 @@ def main():
     # ~3 ms, so a single one scatters by a few per cent).
     walls = sorted(timed_steps(ranks, step, sync_all, args.steps)[0] for _ in range(HEADLINE_WINDOWS))
     wall = walls[len(walls) // 2]
+    if args.dump_outputs:
+        # every window runs steps 0 .. K-1: the set step K-1 wrote holds the last timed step's batch
+        last = (args.steps if args.steps > 0 else args.warmup + len(streams)) - 1
+        dump_outputs(args.dump_outputs, "output" if ranks.rank == 0 else f"output_rank{ranks.rank}",
+                     sets[last % len(sets)][1], geoms, f32, stream)
+
+    def emit(roofline=None, cpu=None, e2e=None, jpeg=None, others=None):
+        for src, dst, _, _ in sets:
+            src.free()
+            dst.free()
+        if ranks.rank == 0:
+            line = bench_line(args.workload, ranks.world, B, args.steps, args.warmup, wall, roofline, cpu, e2e,
+                              manifest(capi, dev, args.full))
+            line["config"]["streams"] = len(streams)
+            line["e2e_jpeg"] = jpeg
+            line["workloads"] = others
+            print(json.dumps(line), flush=True)
+        ranks.close()
+
+    if not args.full:
+        emit()
+        return
     # Per-launch kernel time for the roofline: the same launches back to back
     # on ONE stream, bracketed by HIP events on that stream (the kernel's own),
     # over windows of >= 100 launches and >= 20 ms each, independent of
@@ -669,17 +733,7 @@ def main():
     if ranks.rank == 0 and ranks.world == 1 and not args.no_e2e_jpeg and args.workload == "c2":
         jpeg = e2e_jpeg(dev, no_cpu=args.no_cpu)
 
-    for src, dst, _, _ in sets:
-        src.free()
-        dst.free()
-    if ranks.rank == 0:
-        line = bench_line(args.workload, ranks.world, B, args.steps, args.warmup, wall, roofline, cpu, e2e,
-                          manifest(capi, dev))
-        line["config"]["streams"] = len(streams)
-        line["e2e_jpeg"] = jpeg
-        line["workloads"] = others
-        print(json.dumps(line), flush=True)
-    ranks.close()
+    emit(roofline, cpu, e2e, jpeg, others)
 
 
 def device_sets(capi, dev, sizes, geoms, f32, nsets, seed):
@@ -774,7 +828,8 @@ def split_run(capi, args, ranks, sizes, geoms, f32, B):
     for i in range(args.warmup + 2):
         step(i)
     wall, _ = timed_steps(ranks, step, sync_all, args.steps)
-    line = bench_line(args.workload, D, B, args.steps, args.warmup, wall, None, None, None, manifest(capi, devs[0]))
+    line = bench_line(args.workload, D, B, args.steps, args.warmup, wall, None, None, None,
+                      manifest(capi, devs[0], args.full))
     line["config"]["parallelism"] = (f"split{D} (one process; each step one global batch of {D} x {B} images, one "
                                      f"contiguous slice per device on its own HIP stream; no collective)")
     line["config"]["devices"] = devs

@@ -57,6 +57,24 @@ def test_two_rank_gloo_timing():
     assert line["higher_is_better"] is True
 
 
+def test_plain_and_full_lines_without_a_gpu(tmp_path):
+    """The simulated single-rank run: `--steps` sets the timed steps, `--full`
+    is accepted, and `--dump-outputs` (there is no device batch to write) is an
+    argument error, not a silently missing file."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--warmup", "0", "--simulate", "0.01"]
+    for steps, extra in ((2, []), (4, ["--full"])):
+        p = subprocess.run(cmd + ["--steps", str(steps)] + extra, env=env, capture_output=True, text=True, timeout=60)
+        assert p.returncode == 0, p.stderr
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert line["steps"] == steps and line["ms_per_step"] >= 10.0
+        assert abs(line["value"] - 256 * 1e3 / line["ms_per_step"]) / line["value"] < 0.01
+    p = subprocess.run(cmd + ["--steps", "1", "--dump-outputs", str(tmp_path)], env=env, capture_output=True,
+                       text=True, timeout=60)
+    assert p.returncode == 2 and "--dump-outputs" in p.stderr
+    assert os.listdir(tmp_path) == []
+
+
 def test_bench_launches_its_own_ranks():
     """`bench.py --gpus 2` with no launcher spawns two rank processes (gloo
     barrier + max-over-ranks); the line counts both ranks' batches."""

@@ -29,12 +29,14 @@ if [ "$1" = build ]; then
   exit 0
 fi
 TAG=${2:-abl}
-mkdir -p gpurun_out
-cp mlx-data_amd/libmxd_amd.so gpurun_out/.product.so
+# logs (and the product library while a variant stands in for it) go to $OUT
+OUT=${OUT:-out}
+mkdir -p $OUT
+cp mlx-data_amd/libmxd_amd.so $OUT/.product.so
 for m in 0 $MODES; do
   if [ $m != 0 ]; then cp tools/abl/libmxd_amd_$m.so mlx-data_amd/libmxd_amd.so; fi
-  timeout -k 10 120 python bench.py --no-cpu --no-e2e --no-copy ${BENCH_ARGS:-} > gpurun_out/${TAG}_$m.log 2>&1 || { cp gpurun_out/.product.so mlx-data_amd/libmxd_amd.so; exit 1; }
-  echo "ablate $m $(grep -o '"kernel_ms_per_launch": [0-9.]*' gpurun_out/${TAG}_$m.log)"
+  timeout -k 10 120 python bench.py --full --no-cpu --no-e2e --no-copy ${BENCH_ARGS:-} > $OUT/${TAG}_$m.log 2>&1 || { cp $OUT/.product.so mlx-data_amd/libmxd_amd.so; exit 1; }
+  echo "ablate $m $(grep -o '"kernel_ms_per_launch": [0-9.]*' $OUT/${TAG}_$m.log)"
 done
-cp gpurun_out/.product.so mlx-data_amd/libmxd_amd.so
-rm -f gpurun_out/.product.so
+cp $OUT/.product.so mlx-data_amd/libmxd_amd.so
+rm -f $OUT/.product.so
