@@ -3,7 +3,7 @@
 // across the ABI: every entry point returns a status and leaves a
 // thread-local message), pixel-map dispatch and the process-wide state.  The
 // fused stage's planning, batches and host path live in plan.cpp, batch.cpp
-// and hostpath.cpp (capi_internal.h).
+// and hostpath.cpp / hostjpeg.cpp (capi_internal.h).
 #include "capi_internal.h"
 
 namespace mxd {

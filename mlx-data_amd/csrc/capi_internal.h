@@ -2,8 +2,8 @@
 // capi.cpp (extern "C" entry points, pixel maps, process-wide state),
 // plan.cpp (tap tables, kernel planning, schedule caches), batch.cpp
 // (descriptor workspaces, run_batch: one fused launch per kernel shape) and
-// hostpath.cpp (host-resident and JPEG batches staged through page-locked
-// memory).  Host only.
+// hostpath.cpp / hostjpeg.cpp (host-resident and JPEG batches staged through
+// page-locked memory; hostpath.h).  Host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -236,7 +236,8 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
               const Stored* stored = nullptr);
 
 // ---------------------------------------------------------------------------
-// Host-resident batches (hostpath.cpp).
+// Host-resident batches (hostpath.cpp; JPEG batches: hostjpeg.cpp; what
+// those two share is in hostpath.h).
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
               const mxd_jpeg_image* jpeg = nullptr);
 int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device);

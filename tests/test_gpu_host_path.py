@@ -243,3 +243,91 @@ def test_narrow_return_equals_f32_over_the_link():
     finally:
         for p in pins:
             p.free()
+
+
+@pytest.fixture(scope="module")
+def nine_large():
+    return [synth(1200, 1600, 3, 70 + k) for k in range(9)]
+
+
+@pytest.mark.parametrize("variant", ["u8_host", "f32_host_narrow", "f32_device"])
+def test_raw_call_spanning_three_chunks(nine_large, variant):
+    """Nine 1200x1600 images resized to 400x300 and cropped whole: the
+    footprint is the full source, 4,832 B pitch x 1,200 rows = 5,798,400 B
+    staged per image, so four fit a 24 MiB chunk and five do not -- chunks of
+    4, 4 and 1 images, the third on the first slot again (slot rotation,
+    per-chunk offsets, the copy-out overlapped with the next chunk).  The
+    bytes equal those of nine one-image calls (single chunks, same kernels)."""
+    f32 = variant != "u8_host"
+    dtype = capi.MXD_F32_DIV255 if f32 else capi.MXD_U8
+    row = 400 * 3 * (4 if f32 else 1)
+    size = row * 300
+
+    def run(group):
+        bufs, outs, entries = [], [], []
+        for im in group:
+            if variant == "f32_device":
+                dst = capi.DeviceBuffer(size)
+                bufs.append(dst)
+                dp = dst.ptr
+            else:
+                dst = np.zeros((300, row), np.uint8)
+                dp = dst.ctypes.data
+            outs.append(dst)
+            entries.append(dict(src=im.ctypes.data, src_stride=1600 * 3, src_w=1600, src_h=1200, channels=3,
+                                resize_w=400, resize_h=300, crop_x=0, crop_y=0, crop_w=400, crop_h=300, flip=0,
+                                dst=dp, dst_stride=row))
+        arr, n = capi.make_images(entries)
+        try:
+            if variant == "f32_device":
+                capi.resize_crop_to_device(arr, n, dtype, 0)
+                return [d.download((300, row), np.uint8) for d in outs]
+            capi.resize_crop_host(arr, n, dtype, 0)
+            return outs
+        finally:
+            for b in bufs:
+                b.free()
+
+    capi.narrow_returns(reset=True)
+    got = run(nine_large)
+    assert capi.narrow_returns(reset=True) == (9 if variant == "f32_host_narrow" else 0)
+    for k, im in enumerate(nine_large):
+        want = run([im])[0]
+        assert want.any()
+        assert np.array_equal(got[k], want), k
+
+
+def test_narrow_return_to_an_unaligned_destination():
+    """div255 expansion writes f32 rows with aligned stores, so an image is
+    narrowed only when its destination and row stride are both 4-byte aligned;
+    any other returns f32 over the link (as MXD_TUNE_F32_LINK 1 does) and is
+    not counted in mxd_narrow_returns.  Destinations one byte past a 4-byte
+    boundary with dst_stride = row + 3: the bytes of the aligned call."""
+    imgs = [synth(61, 47, 3, 81), synth(61, 47, 3, 82)]
+    rw, rh = capi.resize_smallest_side_dims(47, 61, 40)
+    cw, ch = 33, 37
+    assert rw >= cw and rh >= ch
+    row = cw * 3 * 4
+
+    def run(shift, stride):
+        outs, entries = [], []
+        for im in imgs:
+            buf = np.zeros(stride * ch + 8, np.uint8)
+            base = buf.ctypes.data
+            off = (-base) % 4 + shift  # `shift` bytes past a 4-byte boundary
+            outs.append((buf, off))
+            entries.append(dict(src=im.ctypes.data, src_stride=47 * 3, src_w=47, src_h=61, channels=3, resize_w=rw,
+                                resize_h=rh, crop_x=(rw - cw) // 2, crop_y=(rh - ch) // 2, crop_w=cw, crop_h=ch,
+                                flip=0, dst=base + off, dst_stride=stride))
+        arr, n = capi.make_images(entries)
+        capi.narrow_returns(reset=True)
+        capi.resize_crop_host(arr, n, capi.MXD_F32_DIV255, 0)
+        count = capi.narrow_returns(reset=True)
+        return [b[o:o + stride * ch].reshape(ch, stride)[:, :row].copy() for b, o in outs], count
+
+    want, narrowed = run(0, row)
+    assert narrowed == 2
+    got, narrowed = run(1, row + 3)
+    assert narrowed == 0
+    for a, b in zip(got, want):
+        assert b.any() and np.array_equal(a, b)

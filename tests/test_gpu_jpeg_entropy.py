@@ -366,7 +366,7 @@ def _segment_bytes(d):
 
 
 def _job_sizes(subs, cap, move=32, warm=24):
-    """hostpath.cpp jpeg_chunk's job split (subsequences per job, warm-up
+    """hostjpeg.cpp jpeg_chunk's job split (jpeghuff.h huff_job_cuts; subsequences per job, warm-up
     included) for segments of `subs` subsequences at a per-job cap."""
     import bisect
 

@@ -507,7 +507,7 @@ bool design_b(const Img& im, const Opts& o, std::vector<Sub>& subs, std::vector<
   return true;
 }
 
-// Round-5 kernel emulation (--jobs 1): hostpath.cpp's job planning and
+// Round-5 kernel emulation (--jobs 1): hostjpeg.cpp's job planning and
 // jpeghuff.hip decode_job, job after job (the look-back sees the previous
 // job's publication), each job's rounds as the workgroup runs them.  Checks
 // the kernel's logic on the CPU; returns false on a mismatch.
@@ -533,16 +533,7 @@ bool emulate_jobs(const Img& im, const Opts& o, const std::vector<int16_t>& host
     N += nsub[g];
   }
   sub_first.push_back(N);
-  const int64_t cap = kHuffThreads - kHuffWarm;
-  const int64_t njob = (N + cap - 1) / cap;
-  std::vector<int64_t> cuts{0};
-  for (int64_t q = 1; q < njob; q++) {
-    int64_t cut = q * N / njob;
-    const int64_t sgi = std::upper_bound(sub_first.begin(), sub_first.end(), cut) - sub_first.begin() - 1;
-    if (cut - sub_first[sgi] <= 32 && sub_first[sgi] > cuts.back()) cut = sub_first[sgi];
-    cuts.push_back(cut);
-  }
-  cuts.push_back(N);
+  const std::vector<int64_t> cuts = huff_job_cuts(sub_first, N, kHuffJobCap);
   std::vector<int16_t> coef(host.size(), 0);
   struct Pub {
     State st;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Phase stamps of the device entropy decode (diagnostic build from
-#   tools/variants.sh build hstamps "-DMXD_HUFF_STAMPS" jpeghuff hostpath)
+#   tools/variants.sh build hstamps "-DMXD_HUFF_STAMPS" jpeghuff hostjpeg)
 # over the C4 and 12 MP batches, summarised by tools/huff_stamps.py.
 #   tools/r05_stamps.sh TAG [datasets]
 set -u

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Phase stamps over several diagnostic builds (tools/variants.sh build NAME
-# "-DMXD_HUFF_STAMPS ..." jpeghuff hostpath), C4 batch only.
+# "-DMXD_HUFF_STAMPS ..." jpeghuff hostjpeg), C4 batch only.
 #   tools/r05_stamps_var.sh TAG NAME...
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

@@ -14,7 +14,7 @@ if [ "$1" = build ]; then
   cd mlx-data_amd
   mkdir -p build/var_$NAME
   OBJS=""
-  for o in resample wave band band_plan pixmap capi plan batch hostpath taps jpeg jpegdev jpeghuff; do
+  for o in resample wave band band_plan pixmap capi plan batch hostpath hostjpeg taps jpeg jpegdev jpeghuff; do
     if [[ " $SRCS " == *" $o "* ]]; then
       src=csrc/$o.hip; [ -f $src ] || src=csrc/$o.cpp
       if [ $o = jpeg ] || [ $o = band_plan ]; then  # host-only C++ (the Makefile's g++ rule)
