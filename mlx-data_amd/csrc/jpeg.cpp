@@ -1209,6 +1209,13 @@ struct Decoder {
     }
     const int ss = u8(), se = u8(), a = u8();
     const int ah = a >> 4, al = a & 15;
+    // jdinput.c per_scan_setup: an interleaved scan's MCU holds at most 10
+    // blocks (D_MAX_BLOCKS_IN_MCU), whatever codes the scan
+    if (ns > 1) {
+      int bpm = 0;
+      for (int i = 0; i < ns; i++) bpm += sc[i]->h * sc[i]->v;
+      if (bpm > 10) fail("Sampling factors too large for interleaved scan");
+    }
     if (device_entropy) {
       record_scan(sc, ns);
       any_scan = true;
@@ -1271,7 +1278,6 @@ struct Decoder {
   // ending at a marker, restart markers RST0..7 in sequence, one per interval.
   void record_scan(Component** sc, int ns) {
     if (scans++ > 0 || progressive || ns != ncomp || (ncomp != 1 && ncomp != 3 && ncomp != 4)) throw NotDevice{};
-    int bpm = 0;
     for (int i = 0; i < ns; i++) {
       if (sc[i]->dc_tbl > 3 || sc[i]->ac_tbl > 3 || !dc[sc[i]->dc_tbl].present || !ac[sc[i]->ac_tbl].present)
           fail("Huffman table was not defined");
@@ -1279,9 +1285,7 @@ struct Decoder {
       std::memcpy(sc[i]->q, quant(*sc[i]), sizeof sc[i]->q);  // latched at the scan
       sc[i]->coded = true;
       scan_comp[i] = (int)(sc[i] - comp);
-      bpm += ns == 1 ? 1 : sc[i]->h * sc[i]->v;
     }
-    if (bpm > 10) throw NotDevice{};  // libjpeg: "Sampling factors too large for interleaved scan"
     scan_ns = ns;
     scan_mcus = ns == 1 ? (int64_t)sc[0]->wib * sc[0]->hib : (int64_t)mcux * mcuy;
     record_segments(scan_mcus);
@@ -1934,6 +1938,13 @@ struct Decoder {
     coefbuf.swap(out);
   }
 
+  // jdsample.c jinit_upsampler: every component of the frame, a CMYK file's
+  // K included, has factors that divide the largest.
+  void check_sampling() const {
+    for (int i = 0; i < ncomp; i++)
+      if (max_h % comp[i].h != 0 || max_v % comp[i].v != 0) fail("Fractional sampling not implemented yet");
+  }
+
   // Components output() reads: grey -> 1; CMYK -> 3 (K is dropped).
   int used_components() const { return ncomp == 1 ? 1 : ncomp == 4 && color_space() == 3 ? 3 : ncomp; }
 
@@ -2039,10 +2050,7 @@ Coefs* decode_coefs(const uint8_t* data, size_t size, std::string* err) {
     if (d.ncomp == 2 || d.color_space() < 0) fail("unhandled format");
     d.finalize();
     // output()'s one failure, checked here so it comes from the decode call
-    // (upsampling reaches it exactly for non-integral factors)
-    if (d.ncomp > 1)
-      for (int i = 0; i < d.used_components(); i++)
-        if (d.max_h % d.comp[i].h != 0 || d.max_v % d.comp[i].v != 0) fail("Fractional sampling not implemented yet");
+    d.check_sampling();
     d.data = nullptr;
     d.size = 0;
     return c.release();
@@ -2069,10 +2077,7 @@ Coefs* parse_held(std::unique_ptr<Coefs> c, std::string* err) {
     if (!d.frame) fail("Invalid JPEG file structure: missing SOF marker");
     if (d.color_space() < 0) fail("unhandled format");
     if (!d.pending) throw NotDevice{};  // no scan
-    // decode_coefs' check: output() reaches it exactly for non-integral factors
-    if (d.ncomp > 1)
-      for (int i = 0; i < d.used_components(); i++)
-        if (d.max_h % d.comp[i].h != 0 || d.max_v % d.comp[i].v != 0) fail("Fractional sampling not implemented yet");
+    d.check_sampling();  // decode_coefs' check
     return c.release();
   } catch (const NotDevice&) {
     return decode_coefs(data, size, err);
@@ -2429,6 +2434,7 @@ bool decode(const uint8_t* data, size_t size, uint8_t* dst, int64_t dst_stride, 
     if (d.width != width || d.height != height) fail("mxd: output buffer does not match the image size");
     if (d.ncomp == 2 || d.color_space() < 0) fail("unhandled format");
     d.finalize();
+    d.check_sampling();
     d.output(dst, dst_stride);
     return true;
   } catch (const Error& e) {

@@ -23,6 +23,22 @@ _AC_SHORT = [0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x21, 0x05, 0xF0]
 _AC_ALL = [0x00, 0xF0] + [(r << 4) | s for r in range(16) for s in range(1, 11)]
 DEEP_AC = ([0, 3, 0, 0, 6, 0, 0, 0, 0, 0, 0, 153, 0, 0, 0, 0], _AC_SHORT + [v for v in _AC_ALL if v not in _AC_SHORT])
 
+# Further tables, so one scan can name four distinct DC and four distinct AC
+# tables: the deep shapes with other symbols on the short codes, fixed-length
+# codes (no code past the look-up), and T.81 Annex K's luminance code lengths
+# (codes up to 16 bits, all in the top of the code space) over this module's
+# own symbol order.
+DEEP_DC2 = (DEEP_DC[0], list(range(11, -1, -1)))
+_AC_SHORT2 = [0x00, 0x01, 0x11, 0x02, 0x03, 0x12, 0x21, 0x31, 0x41]
+DEEP_AC2 = (DEEP_AC[0], _AC_SHORT2 + [v for v in _AC_ALL if v not in _AC_SHORT2])
+FLAT_DC = ([0, 0, 0, 12, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0], list(range(12)))
+FLAT_AC = ([0, 0, 0, 0, 0, 0, 0, 162, 0, 0, 0, 0, 0, 0, 0, 0], _AC_ALL)
+LONG_DC = ([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], list(range(12)))
+LONG_AC = ([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125],
+           [0x00] + sorted((v for v in _AC_ALL if v), key=lambda v: ((v >> 4) + 2 * (v & 15), v)))
+DC_TABLES = [DEEP_DC, FLAT_DC, DEEP_DC2, LONG_DC]
+AC_TABLES = [DEEP_AC, FLAT_AC, DEEP_AC2, LONG_AC]
+
 
 def first_long_prefix(counts):
     """The 11-bit prefix of the first code longer than 11 bits (2048: none) --
@@ -48,33 +64,38 @@ def _codes(table):
 
 
 class _Bits:
+    """Bits, most significant first, into .out with 0xFF bytes stuffed."""
+
     def __init__(self):
         self.out, self.acc, self.n = bytearray(), 0, 0
 
     def put(self, v, n):
         self.acc = (self.acc << n) | (v & ((1 << n) - 1))
         self.n += n
-        while self.n >= 8:
-            self.n -= 8
-            b = (self.acc >> self.n) & 0xFF
-            self.out.append(b)
-            if b == 0xFF:
-                self.out.append(0)
-        self.acc &= (1 << self.n) - 1
+        if self.n >= 512:
+            self._drain()
+
+    def _drain(self):
+        k = self.n & 7
+        self.out += (self.acc >> k).to_bytes(self.n >> 3, "big").replace(b"\xff", b"\xff\x00")
+        self.acc &= (1 << k) - 1
+        self.n = k
 
     def flush(self):
-        if self.n:
-            self.put((1 << (8 - self.n)) - 1, 8 - self.n)
+        if self.n & 7:
+            self.put((1 << (8 - (self.n & 7))) - 1, 8 - (self.n & 7))
+        self._drain()
 
 
 def _category(v):
     return int(abs(int(v))).bit_length()
 
 
-def _dct_blocks(plane, q):
-    """(rows, cols, 64) quantised coefficients in zigzag order."""
+def _dct_blocks(plane, q, grid=None):
+    """(rows, cols, 64) quantised coefficients in zigzag order; grid: the
+    (rows, cols) of blocks to pad the plane to (default: what covers it)."""
     h, w = plane.shape
-    ph, pw = -(-h // 8) * 8, -(-w // 8) * 8
+    ph, pw = (-(-h // 8) * 8, -(-w // 8) * 8) if grid is None else (grid[0] * 8, grid[1] * 8)
     p = np.pad(plane.astype(np.float64), ((0, ph - h), (0, pw - w)), mode="edge") - 128.0
     k = np.arange(8)
     c = np.cos((2 * k[None, :] + 1) * k[:, None] * np.pi / 16) * np.where(k == 0, np.sqrt(1 / 8), 0.5)[:, None]
@@ -84,21 +105,67 @@ def _dct_blocks(plane, q):
     return np.clip(z, -1023, 1023)
 
 
-def encode(pixels, dc=DEEP_DC, ac=DEEP_AC, q=2, restart_mcus=0, coefs=None, adobe=None):
-    """pixels: (H, W) or (H, W, 3) uint8 -> baseline JPEG bytes (4:4:4 when
-    three components, which are written as given: Y, Cb, Cr).  q: the flat
+def _subsample(plane, dh, dw, vx, hx):
+    """Every vx-th row and hx-th column of a full-size plane, (dh, dw) samples."""
+    h, w = plane.shape
+    if (dh, dw, vx, hx) == (h, w, 1, 1):
+        return plane  # as given (a copy's other memory layout can move a float DCT's rounding ties)
+    ys = np.minimum(np.arange(dh) * vx, h - 1)
+    xs = np.minimum(np.arange(dw) * hx, w - 1)
+    return plane[ys][:, xs]
+
+
+def encode(pixels, dc=DEEP_DC, ac=DEEP_AC, q=2, restart_mcus=0, coefs=None, adobe=None, sampling=None, tables=None):
+    """pixels: (H, W) or (H, W, C) uint8 -> baseline JPEG bytes; the
+    components are written as given (Y, Cb, Cr when three).  q: the flat
     quantiser (int) or a 64-entry table in natural order.  coefs: the
     quantised blocks to write instead of the pixels' -- per component a
     (rows, cols, 64) zig-zag array (DC within +-2047 of its neighbour, AC
-    within +-1023) -- pixels then only gives the frame size.  adobe: write an
-    Adobe APP14 marker with this colour transform (0: RGB / CMYK as stored,
-    1: YCbCr, 2: YCCK for four components)."""
+    within +-1023) covering the component's padded block grid -- pixels then
+    only gives the frame size.  adobe: write an Adobe APP14 marker with this
+    colour transform (0: RGB / CMYK as stored, 1: YCbCr, 2: YCCK for four
+    components).
+
+    sampling: (h, v) per component (default all (1, 1)).  Component i holds
+    ceil(W h / max_h) x ceil(H v / max_v) samples (point-sampled from the
+    full-size plane) padded to the MCU grid, mcux h x mcuy v blocks, and the
+    scan is interleaved: per MCU and component v rows of h blocks.  A
+    one-component file is not interleaved (T.81 A.2.2): ceil(W / 8) x
+    ceil(H / 8) blocks in raster order, its factors written in SOF only.
+    restart_mcus counts MCUs of the scan's order.
+
+    tables: (quantiser id, DC table id, AC table id) per component; q, dc
+    and ac are then sequences indexed by those ids (up to four each), all of
+    them written to the file.  Default: one of each, id 0."""
     a = pixels if pixels.ndim == 3 else pixels[:, :, None]
     h, w, nc = a.shape
-    qt = np.full(64, q, np.int64) if np.isscalar(q) else np.asarray(q, np.int64)
-    planes = coefs if coefs is not None else [_dct_blocks(a[:, :, i], qt.reshape(8, 8)) for i in range(nc)]
-    rows, cols = planes[0].shape[:2]
-    dcc, acc = _codes(dc), _codes(ac)
+    samp = [(1, 1)] * nc if sampling is None else [tuple(s) for s in sampling]
+    assert len(samp) == nc and all(1 <= sh <= 4 and 1 <= sv <= 4 for sh, sv in samp)
+    if tables is None:
+        ids, qs, dcs, acs = [(0, 0, 0)] * nc, [q], [dc], [ac]
+    else:
+        ids, qs, dcs, acs = [tuple(t) for t in tables], list(q), list(dc), list(ac)
+        assert len(ids) == nc and max(len(qs), len(dcs), len(acs)) <= 4
+    qts = [np.full(64, x, np.int64) if np.isscalar(x) else np.asarray(x, np.int64) for x in qs]
+    max_h, max_v = max(s[0] for s in samp), max(s[1] for s in samp)
+    mcux, mcuy = -(-w // (8 * max_h)), -(-h // (8 * max_v))
+    if nc == 1:  # non-interleaved: one block per MCU, the factors ignored
+        grids, per_mcu, mcux, mcuy = [None], [(1, 1)], -(-w // 8), -(-h // 8)
+    else:
+        grids, per_mcu = [(mcuy * sv, mcux * sh) for sh, sv in samp], samp
+    if coefs is not None:
+        planes = coefs
+    else:
+        planes = []
+        for i, (sh, sv) in enumerate(samp):
+            if nc == 1:
+                p = a[:, :, 0]
+            else:
+                p = _subsample(a[:, :, i], -(-h * sv // max_v), -(-w * sh // max_h), max_v // sv, max_h // sh)
+            planes.append(_dct_blocks(p, qts[ids[i][0]].reshape(8, 8), grids[i]))
+    rows, cols = mcuy, mcux
+    dccs, accs = [_codes(t) for t in dcs], [_codes(t) for t in acs]
+    order = [(i, by, bx) for i, (sh, sv) in enumerate(per_mcu) for by in range(sv) for bx in range(sh)]
     bits, pred = _Bits(), [0] * nc
     segs, mcu = [], 0
     for r in range(rows):
@@ -107,31 +174,36 @@ def encode(pixels, dc=DEEP_DC, ac=DEEP_AC, q=2, restart_mcus=0, coefs=None, adob
                 bits.flush()
                 segs.append(bytes(bits.out))
                 bits, pred = _Bits(), [0] * nc
-            for i in range(nc):
-                z = planes[i][r, cidx]
+            for i, by, bx in order:
+                dcc, acc = dccs[ids[i][1]], accs[ids[i][2]]
+                z = planes[i][r * per_mcu[i][1] + by, cidx * per_mcu[i][0] + bx]
                 d = int(z[0]) - pred[i]
                 pred[i] = int(z[0])
                 s = _category(d)
                 bits.put(*dcc[s])
                 if s:
                     bits.put(d if d > 0 else d - 1, s)
-                run = 0
-                nz = np.flatnonzero(z[1:])
-                last = nz[-1] + 1 if len(nz) else 0
-                for k in range(1, last + 1):
-                    v = int(z[k])
+                # the block's AC bits gathered in (bv, bn), one put per block
+                zl = z.tolist()
+                prev, bv, bn = 0, 0, 0
+                for k in range(1, 64):
+                    v = zl[k]
                     if v == 0:
-                        run += 1
                         continue
+                    run = k - prev - 1
+                    prev = k
                     while run > 15:
-                        bits.put(*acc[0xF0])
+                        code, n = acc[0xF0]
+                        bv, bn = (bv << n) | code, bn + n
                         run -= 16
-                    s = _category(v)
-                    bits.put(*acc[(run << 4) | s])
-                    bits.put(v if v > 0 else v - 1, s)
-                    run = 0
-                if last < 63:
-                    bits.put(*acc[0x00])
+                    s = abs(v).bit_length()
+                    code, n = acc[(run << 4) | s]
+                    bv = (((bv << n) | code) << s) | ((v if v > 0 else v - 1) & ((1 << s) - 1))
+                    bn += n + s
+                if prev < 63:
+                    code, n = acc[0x00]
+                    bv, bn = (bv << n) | code, bn + n
+                bits.put(bv, bn)
             mcu += 1
     bits.flush()
     segs.append(bytes(bits.out))
@@ -142,13 +214,15 @@ def encode(pixels, dc=DEEP_DC, ac=DEEP_AC, q=2, restart_mcus=0, coefs=None, adob
     out = bytearray(b"\xff\xd8")
     if adobe is not None:
         out += seg(0xEE, b"Adobe" + (100).to_bytes(2, "big") + bytes(4) + bytes([adobe]))
-    out += seg(0xDB, bytes([0]) + bytes(qt[ZIGZAG].astype(np.uint8).tolist()))
+    out += seg(0xDB, b"".join(bytes([k]) + bytes(t[ZIGZAG].astype(np.uint8).tolist()) for k, t in enumerate(qts)))
     out += seg(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([nc]) +
-               b"".join(bytes([i + 1, 0x11, 0]) for i in range(nc)))
-    out += seg(0xC4, bytes([0x00]) + bytes(dc[0]) + bytes(dc[1]) + bytes([0x10]) + bytes(ac[0]) + bytes(ac[1]))
+               b"".join(bytes([i + 1, samp[i][0] << 4 | samp[i][1], ids[i][0]]) for i in range(nc)))
+    out += seg(0xC4, b"".join(bytes([k]) + bytes(t[0]) + bytes(t[1]) for k, t in enumerate(dcs)) +
+               b"".join(bytes([0x10 | k]) + bytes(t[0]) + bytes(t[1]) for k, t in enumerate(acs)))
     if restart_mcus:
         out += seg(0xDD, restart_mcus.to_bytes(2, "big"))
-    out += seg(0xDA, bytes([nc]) + b"".join(bytes([i + 1, 0x00]) for i in range(nc)) + bytes([0, 63, 0]))
+    out += seg(0xDA, bytes([nc]) + b"".join(bytes([i + 1, ids[i][1] << 4 | ids[i][2]]) for i in range(nc)) +
+               bytes([0, 63, 0]))
     for i, s in enumerate(segs):
         if i:
             out += bytes([0xFF, 0xD0 + (i - 1) % 8])

@@ -205,7 +205,9 @@ def test_chunked_batch_of_large_images():
 def _cmyk_files(seed):
     """Four-component files: Pillow CMYK (Adobe transform 0, 1x1 sampling;
     baseline, restart intervals, progressive), and tests/jpeg_enc.py files
-    with an Adobe marker of transform 2 (YCCK) and 0 (CMYK), with restarts."""
+    with an Adobe marker of transform 2 (YCCK) and 0 (CMYK), with restarts.
+    All of these are 1x1; subsampled four-component layouts (Photoshop's
+    2x2, 1x1, 1x1, 2x2 among them) are in tests/test_gpu_jpeg_sampling.py."""
     import jpeg_enc as J
     from PIL import Image
 
