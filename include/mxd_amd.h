@@ -45,7 +45,11 @@ extern "C" {
  * entropy-decoded on the host).
  * 7 (round 6, later): f32 results bound for host memory cross the link as
  * u8 and are expanded (x / 255) on the host -- the knob MXD_TUNE_F32_LINK and
- * the counter mxd_narrow_returns. */
+ * the counter mxd_narrow_returns.
+ * 7, added without a new number (test for the symbols): formatted outputs --
+ * mxd_elem, mxd_layout, mxd_out_format, mxd_out_format_table,
+ * mxd_resize_crop_batch_fmt, mxd_resize_crop_to_device_fmt,
+ * mxd_jpeg_resize_crop_to_device_fmt. */
 #define MXD_ABI_VERSION 7
 
 enum mxd_status {
@@ -415,6 +419,58 @@ int mxd_jpeg_plane_sources(int64_t* count, int32_t reset);
  * link as u8 and expanded on the host (see MXD_TUNE_F32_LINK) since the last
  * reset; reset != 0 zeroes it after reading. */
 int mxd_narrow_returns(int64_t* count, int32_t reset);
+
+/* ---- formatted outputs (ABI 7 additions; feature test: the _fmt symbols) --
+ *
+ * The fused launch can end in the form a training job consumes: normalised
+ * with a per-channel mean / std, in float32, float16 or bfloat16, pixel
+ * interleaved (HWC) or channel planes (CHW).  For a result byte q in channel
+ * c the output element is, in float32 operations each correctly rounded:
+ *
+ *   x   = (float)q / 255.0f                       (MXD_F32_DIV255's value)
+ *   y   = normalize ? (x - mean[c]) / std[c] : x
+ *   out = y converted to elem (float16 / bfloat16: round to nearest even)
+ *
+ * i.e. NumPy's ((u8.astype("float32") / 255) - mean) / std, then
+ * .astype("float16") (or torch's .to(torch.bfloat16)).  mean and std are in
+ * [0, 1] units.  q is exactly what MXD_U8 gives. */
+enum mxd_elem { MXD_ELEM_F32 = 0, MXD_ELEM_F16 = 1, MXD_ELEM_BF16 = 2 };
+enum mxd_layout {
+  MXD_LAYOUT_HWC = 0, /* a pixel's channels contiguous, rows dst_stride bytes apart */
+  MXD_LAYOUT_CHW = 1  /* channel c of pixel (x, y) at dst + c*plane_stride + y*dst_stride + x*elem size */
+};
+
+typedef struct mxd_out_format {
+  int32_t elem;      /* mxd_elem */
+  int32_t layout;    /* mxd_layout */
+  int32_t normalize; /* nonzero: subtract mean[c], divide by std[c] */
+  int32_t reserved;
+  float mean[4], std[4];
+  int64_t plane_stride; /* CHW only: bytes between the channel planes of one image (the same for the whole call) */
+} mxd_out_format;
+
+/* Host only, no device: the channels x 256 output elements (elem-sized,
+ * row-major [channels][256]) a format assigns to the result bytes.  The one
+ * place these values are computed; the kernels look them up. */
+int mxd_out_format_table(const mxd_out_format* fmt, int32_t channels, void* table);
+
+/* mxd_resize_crop_batch / mxd_resize_crop_to_device /
+ * mxd_jpeg_resize_crop_to_device with a formatted output: the same sources,
+ * geometry and device destinations, dst_stride in bytes of formatted rows.
+ * MXD_ERR_INVALID (the message names the field) for a null fmt, an unknown
+ * elem or layout, a zero or non-finite std[c] / non-finite mean[c] (c <
+ * channels) under normalize, a dst or dst_stride that is no multiple of the
+ * element size, CHW with plane_stride < crop_h * dst_stride or no multiple
+ * of the element size, and images of different channel counts in a CHW call.
+ * Images a wave kernel takes are written in their final form by the resize
+ * launch itself; the others (band and general kernels: 4 channels, rows that
+ * are not 4-byte aligned, ...) are resized into a u8 scratch and formatted
+ * by one more launch on the same stream. */
+int mxd_resize_crop_batch_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device,
+                              void* stream);
+int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device);
+int mxd_jpeg_resize_crop_to_device_fmt(const mxd_jpeg_image* images, int32_t n, const mxd_out_format* fmt,
+                                       int32_t device);
 
 /* Diagnostics: where a host-side pipeline's time goes, summed over every
  * thread since the last reset (reset != 0 zeroes them after reading).

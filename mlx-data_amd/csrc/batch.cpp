@@ -110,6 +110,45 @@ WorkspacePool& workspaces() {
   return *p;
 }
 
+// The u8 scratch of a formatted call's two-pass images, one per (device,
+// stream) like the descriptor slots: the band / general kernels write it and
+// format_rows reads it later on the same stream, so it must outlive the call.
+// It only grows; growing first drains the stream that may still read it.  A
+// call holds `mu` from taking the scratch until its last launch is enqueued,
+// so two threads on one stream cannot interleave writers and readers.
+struct FmtScratch {
+  std::mutex mu;
+  uint8_t* ptr = nullptr;
+  size_t cap = 0;
+};
+
+FmtScratch* fmt_scratch(int32_t device, void* stream) {
+  static std::mutex mu;
+  static auto* map = new std::map<std::pair<int32_t, void*>, std::unique_ptr<FmtScratch>>();
+  std::lock_guard<std::mutex> lock(mu);
+  auto& s = (*map)[std::make_pair(device, stream)];
+  if (!s) s = std::make_unique<FmtScratch>();
+  return s.get();
+}
+
+int grow_scratch(FmtScratch* sc, size_t need, void* stream) {
+  if (need <= sc->cap) return MXD_OK;
+  if (sc->ptr) {
+    MXD_HIP(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
+    MXD_HIP(hipFree(sc->ptr));
+    sc->ptr = nullptr;
+    sc->cap = 0;
+  }
+  const size_t cap = std::max<size_t>(need + need / 4, (size_t)1 << 20);
+  MXD_HIP(hipMalloc(reinterpret_cast<void**>(&sc->ptr), cap));
+  sc->cap = cap;
+  return MXD_OK;
+}
+
+// A u8 scratch image's rows: 16-byte aligned, so the band and general
+// kernels plan it as they plan an aligned destination.
+int64_t scratch_stride(const mxd_image& im) { return ((int64_t)im.crop_w * im.channels + 15) & ~(int64_t)15; }
+
 }  // namespace
 
 int32_t strip_chunks(const DevTable& xt, int32_t crop_x, int32_t crop_w, int32_t ox0, int32_t ox1, bool flip,
@@ -278,8 +317,9 @@ int release_descs(Workspace* ws, void* stream, bool hit) {
 }
 
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored) {
+              const Stored* stored, const mxd_out_format* fmt) {
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
+  if (fmt) out_dtype = MXD_U8;  // the form the kernels of a formatted call are planned in
   if (out_dtype != MXD_U8 && out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
   if (n == 0) return MXD_OK;
   const int64_t elem = out_dtype == MXD_F32_DIV255 ? 4 : 1;
@@ -288,9 +328,11 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
   for (int32_t i = 0; i < n; i++) {
     if (int rc = validate(images[i], i)) return rc;
     mixed = mixed || images[i].channels != channels;
-    if (images[i].dst_stride < (int64_t)images[i].crop_w * images[i].channels * elem)
+    if (!fmt && images[i].dst_stride < (int64_t)images[i].crop_w * images[i].channels * elem)
       return fail(MXD_ERR_INVALID, "mxd: dst_stride smaller than an output row");
   }
+  if (fmt)
+    if (int rc = fmt_validate_images(images, n, *fmt)) return rc;
   if (int rc = check_device(device)) return rc;
   if (mixed) {
     // one channel count per launch: one sub-batch per count, in order
@@ -303,7 +345,8 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
           if (stored) ssub.push_back(stored[i]);
         }
       if (!sub.empty())
-        if (int rc = run_batch(sub.data(), (int32_t)sub.size(), out_dtype, device, stream, stored ? ssub.data() : nullptr))
+        if (int rc = run_batch(sub.data(), (int32_t)sub.size(), out_dtype, device, stream, stored ? ssub.data() : nullptr,
+                               fmt))
           return rc;
     }
     return MXD_OK;
@@ -319,10 +362,26 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
         (images[i].rgba_weighted ? a : b).push_back(images[i]);
         if (stored) (images[i].rgba_weighted ? sa : sb).push_back(stored[i]);
       }
-      if (int rc = run_batch(a.data(), (int32_t)a.size(), out_dtype, device, stream, stored ? sa.data() : nullptr))
+      if (int rc = run_batch(a.data(), (int32_t)a.size(), out_dtype, device, stream, stored ? sa.data() : nullptr, fmt))
         return rc;
-      return run_batch(b.data(), (int32_t)b.size(), out_dtype, device, stream, stored ? sb.data() : nullptr);
+      return run_batch(b.data(), (int32_t)b.size(), out_dtype, device, stream, stored ? sb.data() : nullptr, fmt);
     }
+  }
+  // A formatted call plans its kernels as a u8 call does: the wave kernels
+  // exist in the same shapes in every output mode and write any element
+  // alignment, and an image they do not take is resized into u8 scratch rows
+  // (16-byte aligned; their address is set once the plans are known) and
+  // formatted by a second launch.  From here on `images` is a copy whose
+  // destinations are those the resize kernels write.
+  std::vector<mxd_image> fmt_imgs;
+  const mxd_image* const callers = images;
+  if (fmt) {
+    fmt_imgs.assign(images, images + n);
+    for (mxd_image& im : fmt_imgs) {
+      im.dst = reinterpret_cast<void*>((uintptr_t)4096);
+      im.dst_stride = scratch_stride(im);
+    }
+    images = fmt_imgs.data();
   }
   const int32_t f32 = out_dtype == MXD_F32_DIV255 ? 1 : 0;
   const bool no_wave = (g_policy.load() & MXD_POLICY_NO_WAVE) != 0;
@@ -364,6 +423,41 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
     }
   }
   DeviceGuard guard(device);
+  // Formatted call: the wave images' destinations are the caller's; the
+  // others get their scratch rows, and an entry for format_rows.
+  mxd::OutFmtDev ofd{};
+  std::vector<mxd::FmtRowDev> fmt_rows;
+  int32_t fmt_blocks = 0;
+  std::unique_lock<std::mutex> scratch_hold;
+  if (fmt) {
+    ofd.plane_stride = fmt->plane_stride;
+    ofd.elem16 = fmt_elem_size(*fmt) == 2 ? 1 : 0;
+    ofd.chw = fmt->layout == MXD_LAYOUT_CHW ? 1 : 0;
+    if (int rc = fmt_device_table(device, *fmt, channels, &ofd.table)) return rc;
+    size_t need = 0;
+    for (int32_t i = 0; i < n; i++)
+      if (!plans[i].wave) need += (size_t)(scratch_stride(images[i]) * images[i].crop_h + 255) & ~(size_t)255;
+    FmtScratch* sc = nullptr;
+    if (need > 0) {
+      sc = fmt_scratch(device, stream);
+      scratch_hold = std::unique_lock<std::mutex>(sc->mu);
+      if (int rc = grow_scratch(sc, need, stream)) return rc;
+    }
+    size_t at = 0;
+    for (int32_t i = 0; i < n; i++) {
+      mxd_image& im = fmt_imgs[i];
+      if (plans[i].wave) {
+        im.dst = callers[i].dst;
+        im.dst_stride = callers[i].dst_stride;
+        continue;
+      }
+      im.dst = sc->ptr + at;
+      at += (size_t)(im.dst_stride * im.crop_h + 255) & ~(size_t)255;
+      fmt_rows.push_back(mxd::FmtRowDev{static_cast<const uint8_t*>(im.dst), callers[i].dst, im.dst_stride,
+                                        callers[i].dst_stride, im.crop_w, im.crop_h, im.channels, fmt_blocks});
+      fmt_blocks += (im.crop_h + mxd::kFmtRows - 1) / mxd::kFmtRows;
+    }
+  }
   auto fill = [&](ImgDev& d, int32_t i, const ImgPlan& p) {
     const mxd_image& im = images[i];
     const Stored st = stored ? stored[i] : whole(im);
@@ -491,8 +585,8 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
     const ImgPlan& p = plans[order[k]];
     if (groups.empty() || key(order[groups.back().first]) != key(order[k]))
       groups.push_back(
-          {k, 0, 0, 0, mxd::WaveCfg{channels, f32, p.bucket, 0, 0, p.kind, p.s, p.dmax, p.q, p.shift, p.pp, 0, 1,
-                                    p.ycc ? 1 : 0}});
+          {k, 0, 0, 0, mxd::WaveCfg{channels, fmt ? mxd::kWaveOutFmt : f32, p.bucket, 0, 0, p.kind, p.s, p.dmax, p.q,
+                                    p.shift, p.pp, 0, 1, p.ycc ? 1 : 0}});
     groups.back().count++;
   }
   // Source load policy (wave.hip LAUX): streaming (nt) loads when the
@@ -624,6 +718,15 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
     descs.resize(at + unit_tables.size() * 4 / sizeof(ImgDev));
     std::memcpy(reinterpret_cast<void*>(descs.data() + at), unit_tables.data(), unit_tables.size() * 4);
   }
+  // format_rows' entries after them (ImgDev-sized blocks as well): part of
+  // the slot's bytes, so a cached slot is reused only with the same scratch
+  // rows and destinations.  The format itself is a launch argument.
+  const size_t fmt_at = descs.size();
+  if (!fmt_rows.empty()) {
+    const size_t bytes = fmt_rows.size() * sizeof(mxd::FmtRowDev);
+    descs.resize(fmt_at + (bytes + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+    std::memcpy(reinterpret_cast<void*>(descs.data() + fmt_at), fmt_rows.data(), bytes);
+  }
   if (int rc = upload_descs(descs, device, stream, &dev, &hold, &ws, &hit)) return rc;
   const int32_t* tables_dev = reinterpret_cast<const int32_t*>(dev + n);
   // Several launches: fork them over the caller's stream and the workspace's
@@ -668,7 +771,8 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
     } else if (launches[k].kind == 1) {
       Group& g = groups[launches[k].group];
       g.cfg.prio = nfork == 0 ? 1 : 0;  // priorities only where launches never overlap
-      rc = mxd::launch_wave(g.cfg, dev + wbase + g.first, s);
+      rc = fmt ? mxd::launch_wave_fmt(g.cfg, dev + wbase + g.first, ofd, s)
+               : mxd::launch_wave(g.cfg, dev + wbase + g.first, s);
     } else {
       rc = mxd::launch_resample(cfg, dev + wbase + nw, s);
     }
@@ -687,6 +791,12 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
         hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), ws->join[h], 0) != hipSuccess)
       if (launch_rc == MXD_OK) launch_rc = fail(MXD_ERR_DEVICE, "mxd: joining helper streams failed");
   }
+  // The second pass of a formatted call, behind the joins: every resize
+  // kernel that wrote scratch rows is ordered before it on the caller's stream.
+  if (launch_rc == MXD_OK && !fmt_rows.empty() &&
+      mxd::launch_format_rows(reinterpret_cast<const mxd::FmtRowDev*>(dev + fmt_at), (int)fmt_rows.size(), fmt_blocks,
+                              ofd, stream))
+    launch_rc = fail(MXD_ERR_DEVICE, std::string("format_rows launch failed: ") + hipGetErrorString(hipGetLastError()));
   const int rel = release_descs(ws, stream, hit);
   return launch_rc != MXD_OK ? launch_rc : rel;
 }

@@ -236,6 +236,12 @@ int mxd_resize_crop_batch(const mxd_image* images, int32_t n, int32_t out_dtype,
   return run_batch(images, n, out_dtype, device, stream);
 }
 
+int mxd_resize_crop_batch_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device,
+                              void* stream) {
+  if (int rc = fmt_validate(fmt, 0)) return rc;
+  return run_batch(images, n, MXD_U8, device, stream, nullptr, fmt);
+}
+
 int mxd_set_kernel_policy(int32_t policy) { return g_policy.exchange(policy); }
 
 int mxd_set_tuning(int32_t knob, int32_t value) {
@@ -427,6 +433,11 @@ int mxd_resize_crop_to_device(const mxd_image* images, int32_t n, int32_t out_dt
   return host_path(images, n, out_dtype, device, true);
 }
 
+int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device) {
+  if (int rc = fmt_validate(fmt, 0)) return rc;
+  return host_path(images, n, MXD_U8, device, true, nullptr, fmt);
+}
+
 int mxd_memcpy_h2d(void* dst, const void* src, size_t bytes, int32_t device) {
   if (!dst || !src) return fail(MXD_ERR_INVALID, "mxd: null pointer");
   if (int rc = check_device(device)) return rc;
@@ -516,6 +527,12 @@ int mxd_jpeg_resize_crop_host(const mxd_jpeg_image* images, int32_t n, int32_t o
 
 int mxd_jpeg_resize_crop_to_device(const mxd_jpeg_image* images, int32_t n, int32_t out_dtype, int32_t device) {
   return jpeg_path(images, n, out_dtype, device, true);
+}
+
+int mxd_jpeg_resize_crop_to_device_fmt(const mxd_jpeg_image* images, int32_t n, const mxd_out_format* fmt,
+                                       int32_t device) {
+  if (int rc = fmt_validate(fmt, 0)) return rc;
+  return jpeg_path(images, n, MXD_U8, device, true, fmt);
 }
 
 int mxd_host_stats(int64_t* out6, int32_t reset) {

@@ -232,15 +232,33 @@ PlanKey plan_key(const mxd_image& im, const Stored& st);
 // ---------------------------------------------------------------------------
 // Batches (batch.cpp): one fused launch per kernel shape over a batch whose
 // sources are in device memory (or, from the host path, staged: stored[i]).
+// fmt != nullptr: a formatted output (out_dtype is not read).  Images a wave
+// kernel takes are written in that form by the resize launch; the others are
+// resized into a per-(device, stream) u8 scratch and formatted by one
+// format_rows launch that follows on the stream.
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored = nullptr);
+              const Stored* stored = nullptr, const mxd_out_format* fmt = nullptr);
+
+// ---------------------------------------------------------------------------
+// Formatted outputs (outfmt.cpp).
+int32_t fmt_elem_size(const mxd_out_format& fmt);
+// The format itself (null, elem, layout; mean / std of the first `channels` channels).
+int fmt_validate(const mxd_out_format* fmt, int32_t channels);
+// The destinations of a call against it (alignment, strides, one channel count under CHW).
+int fmt_validate_images(const mxd_image* images, int32_t n, const mxd_out_format& fmt);
+// channels x 256 elements: what each result byte of each channel becomes.
+void fmt_table(const mxd_out_format& fmt, int32_t channels, void* table);
+// Its cached device copy.
+int fmt_device_table(int32_t device, const mxd_out_format& fmt, int32_t channels, const void** out);
 
 // ---------------------------------------------------------------------------
 // Host-resident batches (hostpath.cpp; JPEG batches: hostjpeg.cpp; what
 // those two share is in hostpath.h).
+// fmt != nullptr (device destinations only): every chunk's launch writes that format.
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_jpeg_image* jpeg = nullptr);
-int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device);
+              const mxd_jpeg_image* jpeg = nullptr, const mxd_out_format* fmt = nullptr);
+int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
+              const mxd_out_format* fmt = nullptr);
 // mxd_host_stats counters: host-path calls, images, wall ns, device-wait ns,
 // coefficient parses, parse ns
 extern std::atomic<int64_t> g_host_stats[6];

@@ -415,7 +415,8 @@ int jpeg_enqueue(HostCall& c) {
   return MXD_OK;
 }
 
-int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device) {
+int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
+              const mxd_out_format* fmt) {
   if (n < 0 || (n > 0 && !jimg)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
   std::vector<mxd_image> imgs(n);
   for (int32_t i = 0; i < n; i++) {
@@ -446,7 +447,7 @@ int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t 
     m.dst = j.dst;
     m.dst_stride = j.dst_stride;
   }
-  return host_path(imgs.data(), n, out_dtype, device, dst_device, jimg);
+  return host_path(imgs.data(), n, out_dtype, device, dst_device, jimg, fmt);
 }
 
 }  // namespace capi

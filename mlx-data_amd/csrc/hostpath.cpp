@@ -552,7 +552,10 @@ int resize(HostCall& c) {
   const int32_t first = c.cur.first, cn = c.cur.end - first;
   bool mixed = false;
   for (int32_t i = first + 1; i < c.cur.end; i++) mixed = mixed || c.st[i].narrow != c.st[first].narrow;
-  if (!mixed) return run_batch(c.dev_imgs.data(), cn, c.launch_dtype(first), c.device, c.sl->stream, c.where.data());
+  if (!mixed)
+    return run_batch(c.dev_imgs.data(), cn, c.launch_dtype(first), c.device, c.sl->stream, c.where.data(), c.fmt);
+  // (narrowing needs host destinations, a format device ones: never both)
+  if (c.fmt) return fail(MXD_ERR_UNSUPPORTED, "mxd: narrow return within a formatted call");
   int rc = MXD_OK;
   for (int part = 0; part < 2 && rc == MXD_OK; part++) {
     std::vector<mxd_image> pi;
@@ -669,12 +672,19 @@ int raw_enqueue_copies(HostCall& c) {
 // chunk's kernels first decode them into dev_mid.  Every step is common to
 // both sources unless it picks a raw_* or a jpeg_* function.
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_jpeg_image* jpeg) {
+              const mxd_jpeg_image* jpeg, const mxd_out_format* fmt) {
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
+  if (fmt) {
+    // formatted results go to device destinations only; the launches are planned as u8 ones
+    if (!dst_device) return fail(MXD_ERR_UNSUPPORTED, "mxd: formatted outputs need device destinations");
+    out_dtype = MXD_U8;
+  }
   if (out_dtype != MXD_U8 && out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
   if (n == 0) return MXD_OK;
   for (int32_t i = 0; i < n; i++)
     if (int rc = validate(images[i], i)) return rc;
+  if (fmt)
+    if (int rc = fmt_validate_images(images, n, *fmt)) return rc;
   if (int rc = check_device(device)) return rc;
   // Narrow return (round 6): f32 results bound for host memory cross the link
   // as the u8 bytes the same kernels compute before their exact /255 (the
@@ -692,6 +702,7 @@ int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
   CallCount call_count(n);
   HostCall c;
   c.images = images, c.n = n, c.out_dtype = out_dtype, c.device = device, c.dst_device = dst_device, c.jpeg = jpeg;
+  c.fmt = fmt;
 
   // Plan: inputs and outputs per image, then the chunks.
   c.st.resize(n);

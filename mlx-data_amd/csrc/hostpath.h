@@ -114,6 +114,9 @@ struct HostCall {
   int32_t n, out_dtype, device;
   bool dst_device;
   const mxd_jpeg_image* jpeg;  // not null: images[i] is jpeg[i]'s window (hostjpeg.cpp)
+  // not null: every chunk's launch writes this format into the (device)
+  // destinations; out_dtype is then MXD_U8, the form the kernels are planned in
+  const mxd_out_format* fmt = nullptr;
   std::vector<Stage> st;
   std::vector<ChunkRange> chunks;
   HostCtx* ctx = nullptr;

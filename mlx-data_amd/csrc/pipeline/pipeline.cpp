@@ -46,6 +46,9 @@ int64_t itemsize(DType t) {
     case DType::UInt8:
     case DType::Int8:
       return 1;
+    case DType::Float16:
+    case DType::BFloat16:
+      return 2;
     case DType::Int32:
     case DType::Float:
       return 4;
@@ -239,7 +242,19 @@ struct PipeTimer {
   ~PipeTimer() { pipe_counters()[slot].fetch_add(pipe_now() - t0, std::memory_order_relaxed); }
 };
 
-int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device) {
+// The C ABI's form of a plan's output format; planes (CHW) are dense: crop_h
+// rows of `stride` bytes.
+mxd_out_format abi_format(const OutFormat& f, const Job& j) {
+  mxd_out_format o{};
+  o.elem = f.elem;
+  o.layout = f.layout;
+  o.normalize = f.normalize ? 1 : 0;
+  for (int c = 0; c < 4; c++) o.mean[c] = f.mean[c], o.std[c] = f.std[c];
+  o.plane_stride = f.chw() ? j.plan.crop_h * j.stride : 0;
+  return o;
+}
+
+int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device, const OutFormat* fmt = nullptr) {
   g_run_calls.fetch_add(1);
   std::vector<mxd_image> plain;
   std::vector<mxd_jpeg_image> jp;
@@ -254,6 +269,15 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
     }
   }
   g_run_jpeg.fetch_add((int64_t)jp.size());
+  if (fmt) {
+    // formatted outputs: device destinations only (mxd_*_to_device_fmt)
+    if (!dst_device || n == 0) return MXD_OK;
+    const mxd_out_format of = abi_format(*fmt, jobs[0]);
+    if (!jp.empty())
+      if (int rc = mxd_jpeg_resize_crop_to_device_fmt(jp.data(), (int32_t)jp.size(), &of, device)) return rc;
+    if (plain.empty()) return MXD_OK;
+    return mxd_resize_crop_to_device_fmt(plain.data(), (int32_t)plain.size(), &of, device);
+  }
   if (!jp.empty()) {
     const int rc = dst_device ? mxd_jpeg_resize_crop_to_device(jp.data(), (int32_t)jp.size(), dtype, device)
                               : mxd_jpeg_resize_crop_host(jp.data(), (int32_t)jp.size(), dtype, device);
@@ -352,23 +376,71 @@ namespace {
 // source kind) over split_batch's slices: slice 0 on the calling thread, the
 // others on their devices' persistent workers; the first failing slice's
 // message wins.
-void run_host(const std::vector<Job>& jobs, int32_t dtype) {
+std::shared_ptr<void> device_block(int device, int64_t bytes);  // from the device batch pool (below)
+
+// Formatted results bound for host memory, the first version's simple route:
+// the _fmt calls write device destinations only, so the jobs run into a block
+// of the device batch pool laid out like their host destinations and one
+// mxd_memcpy_d2h brings it back (one per job when the destinations are not one
+// dense range).  No chunk overlap between the kernels and the copy.  Returns
+// the error message, empty when all went well.
+std::string run_formatted_to_host(const Job* jobs, size_t n, int device, const OutFormat& fmt) {
+  if (n == 0) return std::string();
+  try {
+    const int64_t es = fmt.elem == MXD_ELEM_F32 ? 4 : 2;
+    std::vector<int64_t> bytes(n);
+    auto* lo = static_cast<uint8_t*>(jobs[0].dst);
+    auto* hi = lo;
+    int64_t sum = 0;
+    for (size_t i = 0; i < n; i++) {
+      bytes[i] = jobs[i].plan.crop_h * jobs[i].plan.crop_w * jobs[i].plan.channels() * es;
+      auto* d = static_cast<uint8_t*>(jobs[i].dst);
+      lo = std::min(lo, d);
+      hi = std::max(hi, d + bytes[i]);
+      sum += bytes[i];
+    }
+    const bool dense = hi - lo == sum;
+    std::shared_ptr<void> block = device_block(device, sum);
+    auto* base = static_cast<uint8_t*>(block.get());
+    std::vector<Job> dev(jobs, jobs + n);
+    int64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+      dev[i].dst = base + (dense ? static_cast<uint8_t*>(jobs[i].dst) - lo : at);
+      at += bytes[i];
+    }
+    if (run_on(dev.data(), n, MXD_U8, device, true, &fmt) != MXD_OK) return mxd_last_error();
+    if (dense) {
+      if (mxd_memcpy_d2h(lo, base, (size_t)sum, device) != MXD_OK) return mxd_last_error();
+    } else {
+      for (size_t i = 0; i < n; i++)
+        if (mxd_memcpy_d2h(jobs[i].dst, dev[i].dst, (size_t)bytes[i], device) != MXD_OK) return mxd_last_error();
+    }
+  } catch (const std::exception& ex) {
+    return ex.what();
+  }
+  return std::string();
+}
+
+void run_host(const std::vector<Job>& jobs, int32_t dtype, const OutFormat* fmt = nullptr) {
   if (jobs.empty()) return;
   const std::vector<int> devs = devices();
   if (devs.empty()) throw std::runtime_error("mxd: no HIP device visible (the image path runs only on the GPU)");
   const size_t n = jobs.size();
   const size_t k = (size_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)devs.size(), (int64_t)n / kMinSliceImages));
   const std::vector<Slice> sl = split_batch((int64_t)n, (int64_t)devs.size(), g_rr.fetch_add(k));
-  if (sl.size() == 1) {
-    check(run_on(jobs.data(), n, dtype, devs[sl[0].device], false));
-    return;
-  }
-  auto slice = [&jobs, dtype, &devs, &sl](size_t s) -> std::string {
-    if (run_on(jobs.data() + sl[s].begin, (size_t)(sl[s].end - sl[s].begin), dtype, devs[sl[s].device], false) !=
-        MXD_OK)
+  auto slice = [&jobs, dtype, &devs, &sl, fmt](size_t s) -> std::string {
+    const Job* first = jobs.data() + sl[s].begin;
+    const size_t count = (size_t)(sl[s].end - sl[s].begin);
+    if (fmt) return run_formatted_to_host(first, count, devs[sl[s].device], *fmt);  // every slice the same format
+    if (run_on(first, count, dtype, devs[sl[s].device], false) != MXD_OK)
       return mxd_last_error();  // thread-local: read on the failing thread
     return std::string();
   };
+  if (sl.size() == 1) {
+    const std::string err = slice(0);
+    if (!err.empty()) throw std::runtime_error(err);
+    return;
+  }
   std::vector<std::future<std::string>> pending;
   for (size_t s = 1; s < sl.size(); s++)
     pending.push_back(device_workers().submit(devs[sl[s].device], [&slice, s] { return slice(s); }));
@@ -420,8 +492,10 @@ Array::Array(DType type, std::vector<int64_t> shape, std::shared_ptr<void> data,
     : type_(type), shape_(std::move(shape)), data_(std::move(data)), device_(device) {}
 
 Array::Array(std::shared_ptr<const ImagePlan> plan)
-    : type_(plan->f32 ? DType::Float : DType::UInt8),
-      shape_({plan->crop_h, plan->crop_w, plan->channels()}),
+    : type_(plan->formatted ? plan->out.type() : plan->f32 ? DType::Float : DType::UInt8),
+      shape_(plan->formatted && plan->out.chw()
+                 ? std::vector<int64_t>{plan->channels(), plan->crop_h, plan->crop_w}
+                 : std::vector<int64_t>{plan->crop_h, plan->crop_w, plan->channels()}),
       plan_(std::move(plan)) {}
 
 Array::Array(std::shared_ptr<const JpegSource> jpeg, int64_t height, int64_t width)
@@ -449,8 +523,14 @@ void* Array::data() const {
   std::lock_guard<std::mutex> lk(mu_);
   if (!data_ && plan_) {
     auto buf = alloc_bytes(nbytes());
-    const int64_t row = shape_[1] * shape_[2] * itemsize(type_);
-    run_host({Job{*plan_, buf.get(), row}}, out_dtype(type_));
+    if (plan_->formatted) {
+      // (device launch + one copy back, see run_formatted_to_host)
+      const int64_t row = plan_->crop_w * (plan_->out.chw() ? 1 : plan_->channels()) * itemsize(type_);
+      run_host({Job{*plan_, buf.get(), row}}, MXD_U8, &plan_->out);
+    } else {
+      const int64_t row = shape_[1] * shape_[2] * itemsize(type_);
+      run_host({Job{*plan_, buf.get(), row}}, out_dtype(type_));
+    }
     data_ = buf;
   }
   if (!data_ && jpeg_) {
@@ -623,15 +703,18 @@ std::shared_ptr<Array> stack_frames(const std::vector<std::shared_ptr<Array>>& f
   const int64_t isz = itemsize(f0->type()), bytes = h * w * c * isz;
   auto* dst = static_cast<uint8_t*>(out->data());
   std::vector<Job> jobs;
+  const OutFormat* fmt = nullptr;  // image_normalize's frames (HWC only): one format, the op's
   for (size_t i = 0; i < frames.size(); i++) {
     const auto& f = frames[i];
     if (f->type() != f0->type()) throw std::runtime_error("applyVideo: frame type inconsistent during transform");
-    if (f->plan() && f->pending())
+    if (f->plan() && f->pending()) {
+      if (f->plan()->formatted) fmt = &f->plan()->out;
       jobs.push_back(Job{*f->plan(), dst + i * bytes, w * c * isz});
-    else
+    } else {
       std::memcpy(dst + i * bytes, f->data(), bytes);
+    }
   }
-  run_host(jobs, out_dtype(f0->type()));  // every pending frame in one launch
+  run_host(jobs, out_dtype(f0->type()), fmt);  // every pending frame in one launch
   return out;
 }
 
@@ -723,6 +806,48 @@ std::shared_ptr<Array> ImageToFloat::apply_image(const std::shared_ptr<Array>& i
   ImagePlan p = view(img);
   p.f32 = true;
   return make(p);
+}
+
+ImageNormalize::ImageNormalize(std::string ikey, std::vector<float> mean, std::vector<float> std,
+                               const std::string& dtype, const std::string& layout, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), mean_(std::move(mean)), std_(std::move(std)) {
+  if (dtype == "float32") fmt_.elem = MXD_ELEM_F32;
+  else if (dtype == "float16") fmt_.elem = MXD_ELEM_F16;
+  else if (dtype == "bfloat16") fmt_.elem = MXD_ELEM_BF16;
+  else throw std::invalid_argument("image_normalize: dtype must be float32, float16 or bfloat16, not '" + dtype + "'");
+  if (layout == "hwc") fmt_.layout = MXD_LAYOUT_HWC;
+  else if (layout == "chw") fmt_.layout = MXD_LAYOUT_CHW;
+  else throw std::invalid_argument("image_normalize: layout must be hwc or chw, not '" + layout + "'");
+  if (mean_.size() > 4 || std_.size() > 4)
+    throw std::invalid_argument("image_normalize: mean / std take one value or one per channel (at most 4)");
+  for (float m : mean_)
+    if (!std::isfinite(m)) throw std::invalid_argument("image_normalize: mean must be finite");
+  for (float s : std_)
+    if (!std::isfinite(s) || s == 0.0f) throw std::invalid_argument("image_normalize: std must be finite and not 0");
+  fmt_.normalize = !mean_.empty() || !std_.empty();
+}
+
+std::shared_ptr<Array> ImageNormalize::apply_image(const std::shared_ptr<Array>& img) const {
+  verify_dimensions(img->shape(1), img->shape(0), img->shape(2));
+  const size_t c = (size_t)img->shape(2);
+  // one value for every channel, or one per channel of this image
+  for (const auto* v : {&mean_, &std_})
+    if (v->size() > 1 && v->size() != c)
+      throw std::invalid_argument("image_normalize: " + std::string(v == &mean_ ? "mean" : "std") + " has " +
+                                  std::to_string(v->size()) + " values, the image " + std::to_string(c) + " channels");
+  ImagePlan p = view(img);
+  p.formatted = true;
+  p.out = fmt_;
+  for (size_t k = 0; k < 4; k++) {
+    if (!mean_.empty()) p.out.mean[k] = mean_.size() == 1 ? mean_[0] : k < c ? mean_[k] : 0.0f;
+    if (!std_.empty()) p.out.std[k] = std_.size() == 1 ? std_[0] : k < c ? std_[k] : 1.0f;
+  }
+  return make(p);
+}
+
+std::shared_ptr<Array> ImageNormalize::apply_video(const std::shared_ptr<Array>& video) const {
+  if (fmt_.chw()) throw std::runtime_error("image_normalize: layout chw takes (H, W, C) images, not (F, H, W, C) videos");
+  return ImageOp::apply_video(video);
 }
 
 namespace {
@@ -1071,6 +1196,31 @@ void fill_t(void* p, int64_t n, double v) {
   std::fill_n(static_cast<T*>(p), n, static_cast<T>(v));
 }
 
+// float32 -> bfloat16 / float16 bits, round to nearest even (pad values).
+uint16_t bf16_bits(float v) {
+  uint32_t f;
+  std::memcpy(&f, &v, 4);
+  if ((f & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+  return (uint16_t)((f + 0x7fffu + ((f >> 16) & 1u)) >> 16);
+}
+
+uint16_t f16_bits(float v) {
+  uint32_t f;
+  std::memcpy(&f, &v, 4);
+  const uint16_t sign = (uint16_t)((f >> 16) & 0x8000u);
+  f &= 0x7fffffffu;
+  if (f > 0x7f800000u) return sign | 0x7e00;
+  if (f >= 0x47800000u) return sign | 0x7c00;  // >= 65536 (65520 and up round to it below)
+  if (f < 0x38800000u) {                       // below 2^-14: a subnormal half, units of 2^-24
+    float a;
+    std::memcpy(&a, &f, 4);
+    return sign | (uint16_t)std::nearbyint(a * 16777216.0f);  // round to nearest even (default mode)
+  }
+  const uint32_t odd = (f >> 13) & 1u;
+  f += 0xc8000000u + 0xfffu + odd;  // exponent rebias 127 -> 15, then round
+  return sign | (uint16_t)(f >> 13);
+}
+
 void fill(Array& a, double v) {
   void* p = a.data();
   const int64_t n = a.size();
@@ -1081,6 +1231,8 @@ void fill(Array& a, double v) {
     case DType::Int64: fill_t<int64_t>(p, n, v); break;
     case DType::Float: fill_t<float>(p, n, v); break;
     case DType::Double: fill_t<double>(p, n, v); break;
+    case DType::Float16: std::fill_n(static_cast<uint16_t*>(p), n, f16_bits((float)v)); break;
+    case DType::BFloat16: std::fill_n(static_cast<uint16_t*>(p), n, bf16_bits((float)v)); break;
     default: break;
   }
 }
@@ -1207,6 +1359,29 @@ DevicePool& device_pool() {
   return *p;
 }
 
+std::shared_ptr<void> device_block(int device, int64_t bytes) { return device_pool().get(device, bytes); }
+
+// The output format the arrays of one key share (null: none has one).
+// image_normalize's arrays batch only with arrays of the same format and
+// channel count, as arrays batch only with arrays of the same type.
+const OutFormat* batch_format(const std::vector<std::shared_ptr<Array>>& arrs) {
+  const ImagePlan* first = nullptr;
+  size_t formatted = 0;
+  for (const auto& a : arrs) {
+    const ImagePlan* p = a->plan() && a->plan()->formatted ? a->plan().get() : nullptr;
+    if (!p) continue;
+    formatted++;
+    if (!first) first = p;
+    if (p->out != first->out)
+      throw std::runtime_error("Array: unexpected different output formats (image_normalize) of arrays in batch");
+    if (p->channels() != first->channels())
+      throw std::runtime_error("Array: unexpected different channel counts of normalised images in batch");
+  }
+  if (formatted != 0 && formatted != arrs.size())
+    throw std::runtime_error("Array: unexpected different output formats (image_normalize) of arrays in batch");
+  return first ? &first->out : nullptr;
+}
+
 }  // namespace
 
 size_t device_pool_bytes(int device) { return device_pool().cached(device); }
@@ -1233,7 +1408,8 @@ namespace {
 // write the batch in place; otherwise the host batch is built and uploaded.
 std::shared_ptr<Array> device_batch(const std::vector<std::shared_ptr<Array>>& arrs,
                                     const std::vector<int64_t>& bshape, const std::vector<int64_t>& stride,
-                                    int64_t item, bool ragged, double pad_value, int dim, bool has_dim, int device) {
+                                    int64_t item, bool ragged, double pad_value, int dim, bool has_dim, int device,
+                                    const OutFormat* fmt) {
   const auto type = arrs.front()->type();
   const int64_t isz = itemsize(type), bytes = shape_size(bshape) * isz;
   std::shared_ptr<void> mem = device_pool().get(device, bytes);
@@ -1244,9 +1420,11 @@ std::shared_ptr<Array> device_batch(const std::vector<std::shared_ptr<Array>>& a
   if (fused) {
     std::vector<Job> jobs;
     auto* base = static_cast<uint8_t*>(ptr);
+    // rows: stride[0] elements apart in (H, W, C); W elements in the planes of (C, H, W)
+    const int64_t row = (fmt && fmt->chw() ? bshape[3] : stride[0]) * isz;
     for (size_t i = 0; i < arrs.size(); i++)
-      jobs.push_back(Job{deferred_plan(arrs[i]), base + (int64_t)i * item * isz, stride[0] * isz});
-    check(run_on(jobs.data(), jobs.size(), out_dtype(type), device, true));
+      jobs.push_back(Job{deferred_plan(arrs[i]), base + (int64_t)i * item * isz, row});
+    check(run_on(jobs.data(), jobs.size(), out_dtype(type), device, true, fmt));
     return res;
   }
   auto host = batch_arrays(arrs, pad_value, dim, has_dim, -1);
@@ -1315,7 +1493,8 @@ std::shared_ptr<Array> batch_arrays(const std::vector<std::shared_ptr<Array>>& a
     for (int d = 0; d < nd; d++)
       if (a->shape()[d] != (has_dim ? bshape[d] : bshape[d + 1]) && !(has_dim && d == dim)) ragged = true;
   const int64_t isz = itemsize(type);
-  if (device >= 0) return device_batch(arrs, bshape, stride, item, ragged, pad_value, dim, has_dim, device);
+  const OutFormat* fmt = batch_format(arrs);
+  if (device >= 0) return device_batch(arrs, bshape, stride, item, ragged, pad_value, dim, has_dim, device, fmt);
   bool images = false;
   for (const auto& a : arrs) images = images || deferred(*a);
   const int64_t total = shape_size(bshape) * isz;
@@ -1330,14 +1509,16 @@ std::shared_ptr<Array> batch_arrays(const std::vector<std::shared_ptr<Array>>& a
     // layout whose pixels fill the batch's pixel slots (same channel count)
     // go to the fused kernels, which write rows straight into the batch; the
     // rest (and a channel count the batch pads) are materialised and copied.
-    if (!has_dim && deferred(*a) && nd == 3 && a->shape(2) == bshape[3]) {
-      launch.push_back(Job{deferred_plan(a), base + off * isz, stride[0] * isz});
+    // A normalised batch takes the launch only when every image fills its
+    // slot (its results come back as one block, run_formatted_to_host).
+    if (!has_dim && deferred(*a) && nd == 3 && a->shape(2) == bshape[3] && !(fmt && ragged)) {
+      launch.push_back(Job{deferred_plan(a), base + off * isz, (fmt && fmt->chw() ? bshape[3] : stride[0]) * isz});
     } else {
       copy_to_strided(base, off, static_cast<const uint8_t*>(a->data()), a->shape(), stride, isz);
     }
     off += has_dim ? item * a->shape(dim) : item;
   }
-  run_host(launch, out_dtype(type));
+  run_host(launch, out_dtype(type), fmt);
   return res;
 }
 

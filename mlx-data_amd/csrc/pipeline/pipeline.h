@@ -33,8 +33,9 @@
 namespace mxd {
 namespace pipe {
 
-// Same order as mlx::data::ArrayType.
-enum class DType { Any, UInt8, Int8, Int32, Int64, Float, Double };
+// Same order as mlx::data::ArrayType; Float16 and BFloat16 (image_normalize's
+// outputs) are appended, so the reference's order stays a prefix.
+enum class DType { Any, UInt8, Int8, Int32, Int64, Float, Double, Float16, BFloat16 };
 int64_t itemsize(DType t);
 
 class Array;
@@ -45,6 +46,25 @@ class Array;
 // launch that resizes / crops it (mxd_jpeg_resize_crop_*); the bytes are the
 // same either way.
 struct JpegSource;
+
+// image_normalize's output format (mxd_out_format without the strides): for a
+// result byte q of channel c the element is ((float)q / 255 - mean[c]) /
+// std[c] in float32 operations (q / 255 alone when !normalize), converted to
+// `elem` (round to nearest even), written pixel-interleaved or as channel
+// planes.
+struct OutFormat {
+  int32_t elem = 0;    // mxd_elem: 0 float32, 1 float16, 2 bfloat16
+  int32_t layout = 0;  // mxd_layout: 0 HWC, 1 CHW
+  bool normalize = false;
+  std::array<float, 4> mean{{0, 0, 0, 0}}, std{{1, 1, 1, 1}};
+  bool operator==(const OutFormat& o) const {
+    return elem == o.elem && layout == o.layout && normalize == o.normalize &&
+           (!normalize || (mean == o.mean && std == o.std));
+  }
+  bool operator!=(const OutFormat& o) const { return !(*this == o); }
+  DType type() const { return elem == 0 ? DType::Float : elem == 1 ? DType::Float16 : DType::BFloat16; }
+  bool chw() const { return layout == 1; }
+};
 
 // Pixel work that has not run yet: take the window (sx, sy, sw, sh) of `src`,
 // resize it to resize_w x resize_h (identity when equal), keep the crop window
@@ -63,6 +83,11 @@ struct ImagePlan {
   // image_to_float: the kernel writes float32 q / 255 (MXD_F32_DIV255)
   // instead of the uint8 q; the array's type is then Float.
   bool f32 = false;
+  // image_normalize: the launch writes `out`'s elements instead
+  // (mxd_*_to_device_fmt); the array's type is out.type() and, with CHW, its
+  // shape (C, crop_h, crop_w).
+  bool formatted = false;
+  OutFormat out;
   int64_t channels() const;
 };
 
@@ -253,6 +278,26 @@ class ImageToFloat : public ImageOp {
  public:
   ImageToFloat(std::string ikey, std::string okey) : ImageOp(std::move(ikey), std::move(okey)) {}
   std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+};
+
+// Fused normalise / cast / layout (an addition to the reference's surface,
+// like ImageToFloat): the reference's post-batch
+// `((x.astype("float32") / 255) - mean) / std`, cast to float16 / bfloat16 and
+// transposed to channels-first if asked, as an image op ahead of batch.  It
+// only marks the pending plan; batch then writes the final tensor from the
+// resize launch.  mean / std: empty (q / 255 only), one value, or one per
+// channel (checked against the image when the op is applied).  (F, H, W, C)
+// videos work with HWC; CHW on one throws.
+class ImageNormalize : public ImageOp {
+ public:
+  ImageNormalize(std::string ikey, std::vector<float> mean, std::vector<float> std, const std::string& dtype,
+                 const std::string& layout, std::string okey);
+  std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+  std::shared_ptr<Array> apply_video(const std::shared_ptr<Array>& video) const override;
+
+ private:
+  std::vector<float> mean_, std_;
+  OutFormat fmt_;
 };
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the

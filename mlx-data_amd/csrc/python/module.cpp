@@ -41,6 +41,7 @@ std::shared_ptr<Array> from_numpy(py::array a) {
   DType t;
   switch (a.dtype().char_()) {
     case 'f': t = DType::Float; break;
+    case 'e': t = DType::Float16; break;
     case 'd': t = DType::Double; break;
     case 'i': t = DType::Int32; break;
     case 'l':
@@ -127,18 +128,23 @@ py::dtype np_dtype(DType t) {
     case DType::Int64: return py::dtype("i8");
     case DType::Float: return py::dtype("f");
     case DType::Double: return py::dtype("d");
+    case DType::Float16: return py::dtype("e");
+    case DType::BFloat16:
+      throw std::runtime_error(
+          "bfloat16 has no NumPy type: build the batch in device memory (batch(..., device=d)) and take it "
+          "through DLPack (torch.from_dlpack)");
     default: throw std::runtime_error("internal error: unknown type");
   }
 }
 
 py::array to_numpy(const std::shared_ptr<Array>& a) {
+  py::dtype dt = np_dtype(a->type());  // (bfloat16 raises before any GPU work)
   void* data;
   {
     // May run the pending GPU work of this array.
     py::gil_scoped_release nogil;
     data = a->data();
   }
-  py::dtype dt = np_dtype(a->type());
   auto* keep = new std::shared_ptr<Array>(a);
   py::capsule owner(keep, [](void* p) { delete static_cast<std::shared_ptr<Array>*>(p); });
   std::vector<int64_t> shape = a->shape(), strides(shape.size());
@@ -158,7 +164,7 @@ struct DLDevice {
   int32_t device_id;
 };
 struct DLDataType {
-  uint8_t code;  // kDLInt 0, kDLUInt 1, kDLFloat 2
+  uint8_t code;  // kDLInt 0, kDLUInt 1, kDLFloat 2, kDLBfloat 4
   uint8_t bits;
   uint16_t lanes;
 };
@@ -186,6 +192,8 @@ DLDataType dl_dtype(DType t) {
     case DType::Int64: return {0, 64, 1};
     case DType::Float: return {2, 32, 1};
     case DType::Double: return {2, 64, 1};
+    case DType::Float16: return {2, 16, 1};
+    case DType::BFloat16: return {4, 16, 1};
     default: throw std::runtime_error("internal error: unknown type");
   }
 }
@@ -275,6 +283,20 @@ std::shared_ptr<T> nogil_owned(T* obj) {
   });
 }
 
+// image_normalize's mean / std: None, a scalar, or one value per channel.
+std::vector<float> channel_values(const py::object& v, const char* what) {
+  if (v.is_none()) return {};
+  if (py::isinstance<py::float_>(v) || py::isinstance<py::int_>(v)) return {v.cast<float>()};
+  if (!py::isinstance<py::str>(v) && !py::isinstance<py::bytes>(v)) {
+    try {
+      auto out = v.cast<std::vector<float>>();
+      if (!out.empty()) return out;
+    } catch (const py::cast_error&) {
+    }
+  }
+  throw std::invalid_argument(std::string("image_normalize: ") + what + " must be None, a number or a sequence of numbers");
+}
+
 // ------------------------------------------------------------ dataset ops
 // The ops every Dataset (Buffer and Stream) carries (wrap_dataset.h).
 template <class D, class Wrap>
@@ -358,7 +380,16 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
           [wrap](const Self& self, const std::string& key, const std::string& output_key) {
             return wrap(self, std::make_shared<ImageToFloat>(key, output_key));
           },
-          py::arg("key"), py::arg("output_key") = "");
+          py::arg("key"), py::arg("output_key") = "")
+      .def(
+          "image_normalize",
+          [wrap](const Self& self, const std::string& key, const py::object& mean, const py::object& std,
+                 const std::string& dtype, const std::string& layout, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageNormalize>(key, channel_values(mean, "mean"),
+                                                               channel_values(std, "std"), dtype, layout, output_key));
+          },
+          py::arg("key"), py::arg("mean") = py::none(), py::arg("std") = py::none(), py::arg("dtype") = "float32",
+          py::arg("layout") = "hwc", py::arg("output_key") = "");
 }
 
 using PadMap = std::unordered_map<std::string, double>;
@@ -390,7 +421,12 @@ PYBIND11_MODULE(_pipeline, m) {
                           "A batch tensor in device memory (batch(..., device=d)): DLPack producer "
                           "(__dlpack__ / __dlpack_device__, kDLROCM), numpy() copies it to the host.")
       .def_property_readonly("shape", [](const DeviceArray& d) { return py::tuple(py::cast(d.a->shape())); })
-      .def_property_readonly("dtype", [](const DeviceArray& d) { return np_dtype(d.a->type()); })
+      .def_property_readonly("dtype",
+                             [](const DeviceArray& d) -> py::object {
+                               // bfloat16 has no NumPy dtype: its name instead
+                               if (d.a->type() == DType::BFloat16) return py::str("bfloat16");
+                               return np_dtype(d.a->type());
+                             })
       .def_property_readonly("device", [](const DeviceArray& d) { return d.a->device(); })
       .def_property_readonly("data_ptr", [](const DeviceArray& d) { return reinterpret_cast<uintptr_t>(d.a->data()); })
       .def_property_readonly("nbytes", [](const DeviceArray& d) { return d.a->nbytes(); })
@@ -541,6 +577,23 @@ PYBIND11_MODULE(_pipeline, m) {
     }
     return check_key(s, key)->pending();
   });
+  // Test hook: sample `idx` of each buffer merged into one batch, so a batch
+  // can hold samples that went through different ops.
+  m.def(
+      "_merge",
+      [](const std::vector<std::shared_ptr<Buffer>>& buffers, int64_t idx, py::object device) {
+        DeviceOut dev;
+        if (!device.is_none()) dev.device = device.cast<int>();
+        Sample out;
+        {
+          py::gil_scoped_release nogil;
+          std::vector<Sample> samples;
+          for (const auto& b : buffers) samples.push_back(b->get(idx));
+          out = merge_batch(samples, {}, {}, dev);
+        }
+        return to_dict(out);
+      },
+      py::arg("buffers"), py::arg("idx") = 0, py::arg("device") = py::none());
   m.def("_plan", [](const std::shared_ptr<Buffer>& b, int64_t idx, const std::string& key) -> py::object {
     Sample s;
     {
@@ -557,6 +610,18 @@ PYBIND11_MODULE(_pipeline, m) {
     d["crop"] = py::make_tuple(p.crop_x, p.crop_y, p.crop_w, p.crop_h);
     d["flip"] = p.flip;
     d["shape"] = a->shape();
+    if (p.formatted) {
+      static const char* const elems[] = {"float32", "float16", "bfloat16"};
+      py::dict f;
+      f["dtype"] = elems[p.out.elem];
+      f["layout"] = p.out.chw() ? "chw" : "hwc";
+      f["normalize"] = p.out.normalize;
+      f["mean"] = std::vector<float>(p.out.mean.begin(), p.out.mean.end());
+      f["std"] = std::vector<float>(p.out.std.begin(), p.out.std.end());
+      d["format"] = f;
+    } else {
+      d["format"] = py::none();
+    }
     return d;
   });
 }

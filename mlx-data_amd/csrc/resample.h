@@ -74,7 +74,9 @@ struct LaunchCfg {
 // bucket; s / dmax = scatter shape; q = output pixels per lane; shift = some
 // image of the launch has a misaligned base.
 struct WaveCfg {
-  int32_t channels, f32, taps, nimgs, nunits;
+  int32_t channels;
+  int32_t f32;  // output mode: 0 u8, 1 f32 q/255, 2 formatted (OutFmtDev; launch_wave_fmt)
+  int32_t taps, nimgs, nunits;
   int32_t kind;
   int32_t s, dmax;
   int32_t q, shift;
@@ -84,6 +86,18 @@ struct WaveCfg {
   int32_t ycc = 0;      // sources are JPEG sample planes (ImgDev::ycc; scatter, p = 4, no shift)
   int32_t nt = 0;       // streaming (nt) source loads (scatter kernels; wave.hip LAUX)
 };
+
+// A formatted output (mxd_out_format) as the kernels see it: a launch
+// argument, never part of the per-image descriptors (a cached descriptor slot
+// serves any format).  table: the device copy of mxd_out_format_table's
+// output for the launch's channel count, channels x 256 elements.
+struct OutFmtDev {
+  const void* table;
+  int64_t plane_stride;  // CHW: bytes between the channel planes of an image
+  int32_t elem16;        // elements are 2 bytes (f16 / bf16), else 4 (f32)
+  int32_t chw;           // channel planes, else pixel interleaved
+};
+constexpr int kWaveOutFmt = 2;  // WaveCfg::f32 of the formatted kernels
 
 // Scatter schedule geometry, shared by the kernel and the host builder:
 // register ring slots for DMAX iterations per group, groups per unrolled
@@ -143,6 +157,25 @@ int wave_plane_floats(int channels, int p);  // LDS floats per wave
 int wave_lanes();
 int launch_wave(const WaveCfg& cfg, const ImgDev* imgs, void* stream);
 bool wave_has_kernel(const WaveCfg& cfg);
+// The formatted-output kernels (wave_fmt.hip; cfg.f32 == kWaveOutFmt): every
+// shape wave.hip has in the other two modes, so wave_has_kernel() of the u8
+// form answers for them too; wave_capacity() forwards to wave_fmt_capacity().
+int launch_wave_fmt(const WaveCfg& cfg, const ImgDev* imgs, const OutFmtDev& fmt, void* stream);
+int wave_fmt_capacity(const WaveCfg& cfg, int device);
+// u8 rows -> formatted rows (format_rows.hip): the second pass of the images
+// the band and general kernels resize.  rows: device array of nimgs entries;
+// one workgroup per kFmtRows rows of an image (nblocks in all, numbered
+// through blk_begin like units through ImgDev::tile_begin).
+constexpr int kFmtRows = 8;
+struct FmtRowDev {
+  const uint8_t* src;  // u8 rows, src_stride apart
+  void* dst;
+  int64_t src_stride, dst_stride;
+  int32_t crop_w, crop_h, channels;
+  int32_t blk_begin;   // first of the image's workgroups among the launch's
+};
+static_assert(sizeof(FmtRowDev) == 48, "FmtRowDev layout");
+int launch_format_rows(const FmtRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
 // Waves of this configuration the device runs at once (occupancy x CUs), 0 if unknown.
 int wave_capacity(const WaveCfg& cfg, int device);
 // Diagnostics: the occupancy API's blocks per CU, the kernel's VGPRs and LDS

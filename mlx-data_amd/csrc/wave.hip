@@ -158,6 +158,25 @@ using Rsrc = __amdgpu_buffer_rsrc_t;
 
 enum Kind { kGather = 0, kScatter = 2 };
 
+// Output modes (template argument OUT; WaveCfg::f32 carries the same value):
+// the u8 result bytes, their exact f32 q/255, or a formatted output
+// (mxd_out_format: normalised, f32 / f16 / bf16, HWC or CHW).  The formatted
+// kernels are one more mode, not six: element size and layout are
+// wave-uniform run-time choices inside it (OutState), and the element a result
+// byte becomes is looked up in an LDS copy of the format's table
+// (mxd_out_format_table), so it equals the table by construction.
+enum Out { kOutU8 = 0, kOutF32 = 1, kOutFmt = 2 };
+
+// What the formatted mode carries to the store; nothing in the other modes.
+template <int OUT>
+struct OutState {};
+template <>
+struct OutState<kOutFmt> {
+  const uint32_t* tab;  // LDS: C x 256 entries, one dword each (16-bit elements in the low half)
+  int64_t plane;        // CHW: bytes between a pixel's channels
+  int e16, chw;         // 2-byte elements; channel planes
+};
+
 // Lane layouts.  Pixel lanes (planar): P source pixels (P*C bytes) per lane;
 // the default P fills 16 bytes (12 for RGB), P = 8 widens an RGB window to
 // 512 pixels (fewer, wider strips per row); the V pass keeps C channel planes.
@@ -448,9 +467,10 @@ __device__ __forceinline__ void wave_lds_sync() {
 #endif
 
 // Horizontal pass of one strip: lane l owns output pixels l + 64 q (q < Q).
-template <class L, bool F32, int T, int Q>
+template <class L, int OUT, int T, int Q>
 struct HStrip {
   static constexpr int C = L::C;
+  static constexpr bool F32 = OUT == kOutF32;
   float wx[Q][T];
   int pos[Q];  // first tap, in pixels from the window start
   int npx;     // output pixels of the strip
@@ -473,7 +493,7 @@ struct HStrip {
 
   // H taps of an output row from the LDS planes, stbir encode, store into
   // drow (the output row, pixel ox0 first).
-  __device__ __forceinline__ void run(const float* planes, char* drow, int lane) const {
+  __device__ __forceinline__ void run(const float* planes, char* drow, int lane, const OutState<OUT>& os) const {
 #pragma unroll
     for (int q = 0; q < Q; q++) {
       const int px = lane + kLanes * q;
@@ -488,6 +508,37 @@ struct HStrip {
       }
       if (q > 0 && kLanes * q >= npx) break;  // uniform: no lane has pixels left
       if ((MXD_ABLATE & 2) && s[0] != -1.0f) continue;
+      if constexpr (OUT == kOutFmt) {
+        if (px < npx) {
+          uint32_t v[C];
+#pragma unroll
+          for (int c = 0; c < C; c++) v[c] = os.tab[c * 256 + (int)s[c]];
+          if (os.chw) {  // uniform: per channel, the wave's 64 pixels are 64 contiguous elements of plane c
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+              char* p = drow + c * os.plane;
+              if (os.e16) store_out(GLOBAL_PTR(uint16_t, p) + px, (uint16_t)v[c]);
+              else store_out(GLOBAL_PTR(uint32_t, p) + px, v[c]);
+            }
+          } else if (os.e16) {  // 2-byte aligned pixels of 2 C bytes: one store per channel
+            auto* d = GLOBAL_PTR(uint16_t, drow) + px * C;
+#pragma unroll
+            for (int c = 0; c < C; c++) store_out(d + c, (uint16_t)v[c]);
+          } else {
+            auto* d = GLOBAL_PTR(uint32_t, drow) + px * C;
+            if constexpr (C == 1) {
+              store_out(d, v[0]);
+            } else if constexpr (C == 2) {
+              store_out(reinterpret_cast<__attribute__((address_space(1))) u32x2*>(d), u32x2{v[0], v[1]});
+            } else if constexpr (C == 3) {
+              store_out(reinterpret_cast<__attribute__((address_space(1))) u32x3*>(d), u32x3{v[0], v[1], v[2]});
+            } else {
+              store_out(reinterpret_cast<__attribute__((address_space(1))) u32x4*>(d), u32x4{v[0], v[1], v[2], v[3]});
+            }
+          }
+        }
+        continue;
+      }
       if constexpr (!F32 && C == 3 && MXD_U8_BPERM != 0) {
         char* row = drow + kLanes * q * 3;  // the chunk's 192 bytes (4-aligned when drow is)
         if ((reinterpret_cast<uintptr_t>(drow) & 3) == 0) {  // uniform
@@ -609,9 +660,10 @@ constexpr int min_waves(int c, int p, int kind, int dmax) {
 }
 
 // One unit (image, band, strip) by the calling wave; planes = its LDS rows.
-template <int C, int P, bool F32, int T, int Q, int KIND, int S, int DMAX, bool SHIFT, bool YCC, int LAUX>
+template <int C, int P, int OUT, int T, int Q, int KIND, int S, int DMAX, bool SHIFT, bool YCC, int LAUX>
 __device__ __forceinline__ void run_unit(const ImgDev* __restrict__ imgs, int nimgs, int per_img, int unit,
-                                         float* __restrict__ planes, int lane, bool prio) {
+                                         float* __restrict__ planes, int lane, bool prio, const OutState<OUT>& os) {
+  constexpr bool F32 = OUT == kOutF32;
   using L = Lay<C, P>;
   constexpr int VC = L::VC, VP = L::VP;
   progress_prio(prio, 0, 1);
@@ -687,7 +739,7 @@ __device__ __forceinline__ void run_unit(const ImgDev* __restrict__ imgs, int ni
       hbase = wp0;
     }
   }
-  HStrip<L, F32, T, Q> hs;
+  HStrip<L, OUT, T, Q> hs;
   // The horizontal weights are loaded once, right after the band's first row
   // loads (their latencies overlap), and retired together with those rows, so
   // the waits the compiler places in the row loop only ever cover row loads.
@@ -696,7 +748,10 @@ __device__ __forceinline__ void run_unit(const ImgDev* __restrict__ imgs, int ni
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   };
 
-  char* dcol = dst + (int64_t)ox0 * C * (F32 ? 4 : 1);
+  // the strip's first column: ox0 pixels of C elements (CHW: of one element)
+  int col_bytes = C * (F32 ? 4 : 1);
+  if constexpr (OUT == kOutFmt) col_bytes = (os.chw ? 1 : C) * (os.e16 ? 2 : 4);
+  char* dcol = dst + (int64_t)ox0 * col_bytes;
   // V row of output row y done: planes to LDS, H pass and store.
   auto finish_row = [&](const float (&acc)[VC][VP], int y) {
     if constexpr ((MXD_ABLATE & 4) != 0) {
@@ -711,7 +766,7 @@ __device__ __forceinline__ void run_unit(const ImgDev* __restrict__ imgs, int ni
     }
     write_planes<L>(planes, acc, lane);
     wave_lds_sync();
-    hs.run(planes, dcol + (int64_t)y * dstride, lane);
+    hs.run(planes, dcol + (int64_t)y * dstride, lane, os);
     wave_lds_sync();
   };
 
@@ -791,7 +846,7 @@ __device__ __forceinline__ void run_unit(const ImgDev* __restrict__ imgs, int ni
 #endif
 }
 
-template <int C, int P, bool F32, int T, int Q, int KIND, int S, int DMAX, bool SHIFT, bool YCC = false,
+template <int C, int P, int OUT, int T, int Q, int KIND, int S, int DMAX, bool SHIFT, bool YCC = false,
           int LAUX = MXD_LOAD_AUX>
 __global__ __launch_bounds__(kWaves* kLanes, min_waves(C, P, KIND, DMAX)) void resample_wave(
     const ImgDev* __restrict__ imgs, int nimgs, int nunits, int per_img, int prio) {
@@ -807,43 +862,98 @@ __global__ __launch_bounds__(kWaves* kLanes, min_waves(C, P, KIND, DMAX)) void r
     for (int i = 0; i < L::PAD; i += kLanes)
       if (i + lane < L::PAD) planes[c * PL + L::WPX + i + lane] = 0.0f;  // padded taps read zeros
   if (unit < nunits)
-    run_unit<C, P, F32, T, Q, KIND, S, DMAX, SHIFT, YCC, LAUX>(imgs, nimgs, per_img, unit, planes, lane,
-                                                    __builtin_amdgcn_readfirstlane(prio) != 0);
+    run_unit<C, P, OUT, T, Q, KIND, S, DMAX, SHIFT, YCC, LAUX>(imgs, nimgs, per_img, unit, planes, lane,
+                                                    __builtin_amdgcn_readfirstlane(prio) != 0, OutState<OUT>{});
+}
+
+// The formatted-output form of the same kernel (wave_fmt.hip instantiates
+// it).  The workgroup first copies the format's table into LDS behind its
+// waves' planes -- the kernel's only workgroup barrier; every wave reaches
+// it, also one without a unit -- and the H pass looks each result byte up
+// there instead of computing q / 255.
+template <int C, int P, int T, int Q, int KIND, int S, int DMAX, bool SHIFT, bool YCC = false,
+          int LAUX = MXD_LOAD_AUX>
+__global__ __launch_bounds__(kWaves* kLanes, min_waves(C, P, KIND, DMAX)) void resample_wave_fmt(
+    const ImgDev* __restrict__ imgs, int nimgs, int nunits, int per_img, int prio, OutFmtDev fmt) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  using L = Lay<C, P>;
+  constexpr int PL = L::PL;
+  const int lane = threadIdx.x & (kLanes - 1);
+  const int unit = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x) * kWaves + (threadIdx.x >> 6));
+  float* __restrict__ planes = smem + (threadIdx.x >> 6) * (L::VC * PL);
+#pragma unroll
+  for (int c = 0; c < L::VC; c++)
+#pragma unroll
+    for (int i = 0; i < L::PAD; i += kLanes)
+      if (i + lane < L::PAD) planes[c * PL + L::WPX + i + lane] = 0.0f;  // padded taps read zeros
+  uint32_t* tab = reinterpret_cast<uint32_t*>(smem + kWaves * (L::VC * PL));
+  const int e16 = __builtin_amdgcn_readfirstlane(fmt.elem16);
+  for (int i = threadIdx.x; i < C * 256; i += kWaves * kLanes)
+    tab[i] = e16 ? (uint32_t)static_cast<const uint16_t*>(fmt.table)[i] : static_cast<const uint32_t*>(fmt.table)[i];
+  __syncthreads();
+  if (unit < nunits) {
+    OutState<kOutFmt> os;
+    os.tab = tab;
+    os.plane = fmt.plane_stride;
+    os.e16 = e16;
+    os.chw = __builtin_amdgcn_readfirstlane(fmt.chw);
+    run_unit<C, P, kOutFmt, T, Q, KIND, S, DMAX, SHIFT, YCC, LAUX>(imgs, nimgs, per_img, unit, planes, lane,
+                                                                 __builtin_amdgcn_readfirstlane(prio) != 0, os);
+  }
 }
 
 using WaveKernel = void (*)(const ImgDev*, int, int, int, int);
+using WaveFmtKernel = void (*)(const ImgDev*, int, int, int, int, OutFmtDev);
+
+// The kernel of an output mode: its type, and the instantiation for a shape.
+template <int OUT>
+struct KernelOf {
+  using type = WaveKernel;
+};
+template <>
+struct KernelOf<kOutFmt> {
+  using type = WaveFmtKernel;
+};
+template <int C, int P, int OUT, int T, int Q, int KIND, int S, int DMAX, bool SHIFT, bool YCC = false,
+          int LAUX = MXD_LOAD_AUX>
+typename KernelOf<OUT>::type wave_kernel() {
+  if constexpr (OUT == kOutFmt)
+    return resample_wave_fmt<C, P, T, Q, KIND, S, DMAX, SHIFT, YCC, LAUX>;
+  else
+    return resample_wave<C, P, OUT, T, Q, KIND, S, DMAX, SHIFT, YCC, LAUX>;
+}
 
 constexpr int default_p(int c) { return c == 1 ? 16 : c == 2 ? 8 : 4; }
 
-template <int C, bool F32, int T, int Q>
-WaveKernel select_gather(const WaveCfg& cfg) {
+template <int C, int OUT, int T, int Q>
+typename KernelOf<OUT>::type select_gather(const WaveCfg& cfg) {
   constexpr int P = default_p(C);
-  if (cfg.shift) return resample_wave<C, P, F32, T, Q, kGather, 1, 1, true>;
-  return resample_wave<C, P, F32, T, Q, kGather, 1, 1, false>;
+  if (cfg.shift) return wave_kernel<C, P, OUT, T, Q, kGather, 1, 1, true>();
+  return wave_kernel<C, P, OUT, T, Q, kGather, 1, 1, false>();
 }
 
-template <int C, bool F32, int Q>
-WaveKernel select_taps(const WaveCfg& cfg) {
+template <int C, int OUT, int Q>
+typename KernelOf<OUT>::type select_taps(const WaveCfg& cfg) {
   switch (cfg.taps) {
-    case 2: return select_gather<C, F32, 2, Q>(cfg);
-    case 3: return select_gather<C, F32, 3, Q>(cfg);
-    case 4: return select_gather<C, F32, 4, Q>(cfg);
-    case 6: return select_gather<C, F32, 6, Q>(cfg);
-    case 8: return select_gather<C, F32, 8, Q>(cfg);
-    case 10: return select_gather<C, F32, 10, Q>(cfg);
-    case 12: return select_gather<C, F32, 12, Q>(cfg);
-    case 17: return select_gather<C, F32, 17, Q>(cfg);
+    case 2: return select_gather<C, OUT, 2, Q>(cfg);
+    case 3: return select_gather<C, OUT, 3, Q>(cfg);
+    case 4: return select_gather<C, OUT, 4, Q>(cfg);
+    case 6: return select_gather<C, OUT, 6, Q>(cfg);
+    case 8: return select_gather<C, OUT, 8, Q>(cfg);
+    case 10: return select_gather<C, OUT, 10, Q>(cfg);
+    case 12: return select_gather<C, OUT, 12, Q>(cfg);
+    case 17: return select_gather<C, OUT, 17, Q>(cfg);
     default: return nullptr;
   }
 }
 
-template <int C, bool F32>
-WaveKernel select_q(const WaveCfg& cfg) {
+template <int C, int OUT>
+typename KernelOf<OUT>::type select_q(const WaveCfg& cfg) {
   if (cfg.p != default_p(C)) return nullptr;
   switch (cfg.q) {
-    case 1: return select_taps<C, F32, 1>(cfg);
-    case 2: return select_taps<C, F32, 2>(cfg);
-    case 4: return select_taps<C, F32, 4>(cfg);
+    case 1: return select_taps<C, OUT, 1>(cfg);
+    case 2: return select_taps<C, OUT, 2>(cfg);
+    case 4: return select_taps<C, OUT, 4>(cfg);
     default: return nullptr;
   }
 }
@@ -852,22 +962,22 @@ WaveKernel select_q(const WaveCfg& cfg) {
 // shapes of resize_smallest_side 256/512 from 200p..4K sources: downsampling
 // by the tent filter reaches each source row from at most two output rows
 // (S = 2), DMAX = ceil(in / out).
-template <bool F32>
-WaveKernel select_scatter(const WaveCfg& cfg) {
+template <int OUT>
+typename KernelOf<OUT>::type select_scatter(const WaveCfg& cfg) {
   if (cfg.channels != 3) return nullptr;
 #define MXD_SCATTER(S_, D_, T_, Q_, P_)                                                           \
   if (cfg.s == S_ && cfg.dmax == D_ && cfg.taps == T_ && cfg.q == Q_ && cfg.p == P_)              \
-    return cfg.ycc ? (P_ == 4 && !cfg.shift ? resample_wave<3, 4, F32, T_, Q_, kScatter, S_, D_, false, true> \
+    return cfg.ycc ? (P_ == 4 && !cfg.shift ? wave_kernel<3, 4, OUT, T_, Q_, kScatter, S_, D_, false, true>() \
                                             : nullptr)                                            \
-           : cfg.shift ? (cfg.nt ? resample_wave<3, P_, F32, T_, Q_, kScatter, S_, D_, true, false, kLoadNt> \
-                                 : resample_wave<3, P_, F32, T_, Q_, kScatter, S_, D_, true>)     \
-                       : (cfg.nt ? resample_wave<3, P_, F32, T_, Q_, kScatter, S_, D_, false, false, kLoadNt> \
-                                 : resample_wave<3, P_, F32, T_, Q_, kScatter, S_, D_, false>);
+           : cfg.shift ? (cfg.nt ? wave_kernel<3, P_, OUT, T_, Q_, kScatter, S_, D_, true, false, kLoadNt>() \
+                                 : wave_kernel<3, P_, OUT, T_, Q_, kScatter, S_, D_, true>())     \
+                       : (cfg.nt ? wave_kernel<3, P_, OUT, T_, Q_, kScatter, S_, D_, false, false, kLoadNt>() \
+                                 : wave_kernel<3, P_, OUT, T_, Q_, kScatter, S_, D_, false>());
   // byte lanes (P = 16): any base alignment, no realignment variant
 #define MXD_SCATTER_B(S_, D_, T_, Q_)                                                             \
   if (cfg.s == S_ && cfg.dmax == D_ && cfg.taps == T_ && cfg.q == Q_ && cfg.p == 16 && !cfg.ycc)  \
-    return cfg.nt ? resample_wave<3, 16, F32, T_, Q_, kScatter, S_, D_, false, false, kLoadNt>    \
-                  : resample_wave<3, 16, F32, T_, Q_, kScatter, S_, D_, false>;
+    return cfg.nt ? wave_kernel<3, 16, OUT, T_, Q_, kScatter, S_, D_, false, false, kLoadNt>()    \
+                  : wave_kernel<3, 16, OUT, T_, Q_, kScatter, S_, D_, false>();
   MXD_SCATTER(2, 4, 8, 2, 8)    // 960 -> 256 (C2)
 #ifndef MXD_ONLY_C2  // register-count checks of one kernel (tools/wave_regs.sh)
   MXD_SCATTER(2, 4, 8, 1, 4)
@@ -908,22 +1018,31 @@ WaveKernel select_scatter(const WaveCfg& cfg) {
   return nullptr;
 }
 
-WaveKernel select_kernel(const WaveCfg& cfg) {
+// The kernel of cfg in one output mode (nullptr: none).
+template <int OUT>
+typename KernelOf<OUT>::type select_mode(const WaveCfg& cfg) {
+  if (cfg.kind == kScatter) return select_scatter<OUT>(cfg);
 #ifdef MXD_ONLY_C2
-  return cfg.kind == kScatter && cfg.f32 ? select_scatter<true>(cfg) : nullptr;
+  return nullptr;
 #endif
-  if (cfg.kind == kScatter) return cfg.f32 ? select_scatter<true>(cfg) : select_scatter<false>(cfg);
   if (cfg.ycc) return nullptr;  // JPEG plane sources: scatter kernels only
-  switch (cfg.channels * 2 + (cfg.f32 ? 1 : 0)) {
-    case 2: return select_q<1, false>(cfg);
-    case 3: return select_q<1, true>(cfg);
-    case 4: return select_q<2, false>(cfg);
-    case 5: return select_q<2, true>(cfg);
-    case 6: return select_q<3, false>(cfg);
-    case 7: return select_q<3, true>(cfg);
+  switch (cfg.channels) {
+    case 1: return select_q<1, OUT>(cfg);
+    case 2: return select_q<2, OUT>(cfg);
+    case 3: return select_q<3, OUT>(cfg);
     default: return nullptr;
   }
 }
+
+#ifndef MXD_WAVE_FMT_TU
+WaveKernel select_kernel(const WaveCfg& cfg) {
+  if (cfg.f32 == kOutFmt) return nullptr;  // wave_fmt.hip's kernels (launch_wave_fmt)
+#ifdef MXD_ONLY_C2
+  return cfg.f32 ? select_mode<kOutF32>(cfg) : nullptr;
+#endif
+  return cfg.f32 ? select_mode<kOutF32>(cfg) : select_mode<kOutU8>(cfg);
+}
+#endif
 
 int lds_bytes(const WaveCfg& cfg) { return kWaves * wave_plane_floats(cfg.channels, cfg.p) * (int)sizeof(float); }
 
@@ -933,6 +1052,36 @@ constexpr int plane_floats() {
 }
 
 }  // namespace
+
+#ifdef MXD_WAVE_FMT_TU
+// ---- wave_fmt.hip: the formatted-output kernels and their launch ----------
+namespace {
+// the planes of the workgroup's waves, then the format table (one dword per entry)
+int lds_bytes_fmt(const WaveCfg& cfg) { return lds_bytes(cfg) + cfg.channels * 256 * (int)sizeof(uint32_t); }
+}  // namespace
+
+int launch_wave_fmt(const WaveCfg& cfg, const ImgDev* imgs, const OutFmtDev& fmt, void* stream) {
+  const WaveFmtKernel k = select_mode<kOutFmt>(cfg);
+  if (!k) return -2;
+  const int blocks = (cfg.nunits + kWaves - 1) / kWaves;
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(kWaves * kLanes), lds_bytes_fmt(cfg), reinterpret_cast<hipStream_t>(stream),
+                     imgs, cfg.nimgs, cfg.nunits, cfg.per_img, cfg.prio, fmt);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int wave_fmt_capacity(const WaveCfg& cfg, int device) {
+  const WaveFmtKernel k = select_mode<kOutFmt>(cfg);
+  if (!k) return 0;
+  int blocks = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(k), kWaves * kLanes,
+                                                   lds_bytes_fmt(cfg)) != hipSuccess)
+    return 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
+  return blocks * kWaves * cus;
+}
+
+}  // namespace mxd
+#else
 
 int wave_taps_bucket(int taps) {
   static const int kB[] = {2, 3, 4, 6, 8, 10, 12, 17, 24, 32};
@@ -1023,6 +1172,7 @@ int wave_kernel_info(const WaveCfg& cfg, int device, int* api_blocks, int* vgprs
 }
 
 int wave_capacity(const WaveCfg& cfg, int device) {
+  if (cfg.f32 == kOutFmt) return wave_fmt_capacity(cfg, device);
   const WaveKernel k = select_kernel(cfg);
   if (!k) return 0;
   int blocks = 0, cus = 0;
@@ -1035,7 +1185,8 @@ int wave_capacity(const WaveCfg& cfg, int device) {
 
 }  // namespace mxd
 
-#if MXD_STAMPS
+#endif  // MXD_WAVE_FMT_TU
+#if MXD_STAMPS && !defined(MXD_WAVE_FMT_TU)
 // Copies the first n units' (start, end) stamps of the last stamped launches.
 extern "C" int mxd_debug_stamps(unsigned long long* host, int n) {
   if (n > mxd::kMaxStamped) n = mxd::kMaxStamped;

@@ -38,7 +38,15 @@ EXPORTS = (
     "mxd_jpeg_coefs_info", "mxd_jpeg_coefs_finish",
     "mxd_jpeg_resize_crop_host", "mxd_jpeg_resize_crop_to_device", "mxd_jpeg_plane_sources", "mxd_host_stats", "mxd_device_stats", "mxd_copy_bandwidth_policy",
     "mxd_narrow_returns",
+    "mxd_out_format_table", "mxd_resize_crop_batch_fmt", "mxd_resize_crop_to_device_fmt",
+    "mxd_jpeg_resize_crop_to_device_fmt",
 )
+
+MXD_ELEM_F32 = 0
+MXD_ELEM_F16 = 1
+MXD_ELEM_BF16 = 2
+MXD_LAYOUT_HWC = 0
+MXD_LAYOUT_CHW = 1
 
 MXD_AFFINE = 0
 MXD_CHANNEL_REDUCTION = 1
@@ -132,6 +140,20 @@ class MxdJpegImage(ctypes.Structure):
     ]
 
 
+class MxdOutFormat(ctypes.Structure):
+    """struct mxd_out_format (include/mxd_amd.h): a formatted output."""
+
+    _fields_ = [
+        ("elem", ctypes.c_int32),
+        ("layout", ctypes.c_int32),
+        ("normalize", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("mean", ctypes.c_float * 4),
+        ("std", ctypes.c_float * 4),
+        ("plane_stride", ctypes.c_int64),
+    ]
+
+
 class MxdError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(msg)
@@ -213,6 +235,50 @@ def make_images(entries):
 
 def resize_crop_batch(images, n, out_dtype, device=0, stream=None):
     check(lib().mxd_resize_crop_batch(images, n, out_dtype, device, ctypes.c_void_p(stream)))
+
+
+ELEM_SIZE = {MXD_ELEM_F32: 4, MXD_ELEM_F16: 2, MXD_ELEM_BF16: 2}
+
+
+def make_out_format(elem=MXD_ELEM_F32, layout=MXD_LAYOUT_HWC, mean=None, std=None, plane_stride=0):
+    """An mxd_out_format: mean / std None = q/255 only, else a scalar or one
+    value per channel (a scalar fills all four)."""
+    f = MxdOutFormat()
+    f.elem, f.layout, f.plane_stride = int(elem), int(layout), int(plane_stride)
+    f.normalize = 0 if mean is None and std is None else 1
+    for k in range(4):
+        f.mean[k], f.std[k] = 0.0, 1.0
+    for name, v in (("mean", mean), ("std", std)):
+        if v is None:
+            continue
+        v = np.atleast_1d(np.asarray(v, np.float32))
+        v = np.repeat(v, 4) if len(v) == 1 else v
+        for k in range(min(4, len(v))):
+            getattr(f, name)[k] = float(v[k])
+    return f
+
+
+def out_format_table(fmt, channels):
+    """mxd_out_format_table: the (channels, 256) elements the result bytes
+    become, as uint32 (float32 bits) or uint16 (float16 / bfloat16 bits)."""
+    out = np.zeros((channels, 256), np.uint32 if fmt.elem == MXD_ELEM_F32 else np.uint16)
+    check(lib().mxd_out_format_table(ctypes.byref(fmt) if fmt is not None else None, channels,
+                                     out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def resize_crop_batch_fmt(images, n, fmt, device=0, stream=None):
+    check(lib().mxd_resize_crop_batch_fmt(images, n, ctypes.byref(fmt) if fmt is not None else None, device,
+                                          ctypes.c_void_p(stream)))
+
+
+def resize_crop_to_device_fmt(images, n, fmt, device=0):
+    """Host sources, formatted device destinations (mxd_resize_crop_to_device_fmt)."""
+    check(lib().mxd_resize_crop_to_device_fmt(images, n, ctypes.byref(fmt) if fmt is not None else None, device))
+
+
+def jpeg_resize_crop_to_device_fmt(images, n, fmt, device=0):
+    check(lib().mxd_jpeg_resize_crop_to_device_fmt(images, n, ctypes.byref(fmt) if fmt is not None else None, device))
 
 
 def set_kernel_policy(policy):

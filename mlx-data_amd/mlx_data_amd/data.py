@@ -26,6 +26,30 @@ import torch before this package when torch consumes them, so both share one
 HIP runtime.  Reading an unbatched image materialises it with its own launch.
 There is no CPU resize: without a visible GPU the image ops raise.
 
+``image_normalize(key, mean=None, std=None, dtype="float32", layout="hwc",
+output_key="")`` (with ``image_normalize_if``; the second addition to the
+surface) ends the chain in the form a training step consumes:
+``((x.astype("float32") / 255) - mean) / std`` in float32 operations, cast to
+``float32``, ``float16`` or ``bfloat16`` (round to nearest even), as
+``(B, H, W, C)`` (``hwc``) or ``(B, C, H, W)`` (``chw``).  ``mean`` / ``std``
+are ``None`` (``x / 255`` only), a number, or one value per channel, in [0, 1]
+units like ``torchvision.transforms.Normalize`` after ``ToTensor``.  Like
+``image_to_float`` it only marks the pending image, so ``batch(n, device=d)``
+writes the final tensor from the resize launch itself -- no second pass over
+the batch -- and ``DeviceArray`` exports it through DLPack (float16 as
+``kDLFloat``/16, bfloat16 as ``kDLBfloat``/16).  No image op may follow it; a
+batch takes one format and one channel count per key; ragged batches pad with
+zeros (or ``pad``); videos ``(F, H, W, C)`` take ``hwc`` only.
+
+First version of the host side: a host batch (``batch(n)`` without
+``device=``) and a direct read of an unbatched normalised image are produced
+by the same device calls into a block of the device batch pool and copied back
+with one device-to-host copy, without the chunk overlap the uint8 and
+``image_to_float`` host batches have.  float32 and float16 come back as NumPy
+arrays; bfloat16 has no NumPy type, so a host batch of it (and
+``DeviceArray.numpy()``) raises ``RuntimeError``: use ``device=`` and
+``torch.from_dlpack``.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole
@@ -84,7 +108,7 @@ def _add_if_variants(cls):
     unchanged (``Dataset::*_if``, ``Dataset.cpp``)."""
     for name in ("key_transform", "load_image", "image_resize_smallest_side", "image_resize",
                  "image_center_crop", "image_random_crop", "image_random_h_flip", "image_random_area_crop",
-                 "image_rotate", "image_channel_reduction", "image_to_float"):
+                 "image_rotate", "image_channel_reduction", "image_to_float", "image_normalize"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 

@@ -10,5 +10,5 @@ out=$(mktemp -d)
   -DMXD_ONLY_C2 "$@" --offload-device-only -S csrc/wave.hip -o "$out/w.s"
 # C2's product kernel: resample_wave<3, 8, f32, 8, 2, scatter, 2, 4, no shift, RGB, nt>
 grep -E "^\s+\.name:\s+_Z.*resample_wave|^\s+\.(vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count):" "$out/w.s" |
-  grep -A4 "resample_waveILi3ELi8ELb1ELi8ELi2ELi2ELi2ELi4ELb0ELb0ELi2E"
+  grep -A4 "resample_waveILi3ELi8ELi1ELi8ELi2ELi2ELi2ELi4ELb0ELb0ELi2E"
 rm -rf "$out"
