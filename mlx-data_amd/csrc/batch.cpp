@@ -1,6 +1,7 @@
 // batch.cpp -- run_batch (capi_internal.h): per-stream descriptor
-// workspaces and the fused launches of one batch (band, wave and general
-// kernels, forked over helper streams when a batch needs several).
+// workspaces and the fused launches of one batch's layout (batch_layout.cpp:
+// band, wave and general kernels, forked over helper streams when a batch
+// needs several).
 #include <atomic>
 #include <deque>
 
@@ -9,10 +10,6 @@
 namespace mxd {
 namespace capi {
 namespace {
-
-// A call whose wave-kernel sources total at least this many bytes loads them
-// with the streaming (nt) policy (half the 256 MB Infinity Cache).
-constexpr int64_t kNtSourceBytes = (int64_t)128 << 20;
 
 struct Workspace {
   std::mutex mu;
@@ -144,10 +141,6 @@ int grow_scratch(FmtScratch* sc, size_t need, void* stream) {
   sc->cap = cap;
   return MXD_OK;
 }
-
-// A u8 scratch image's rows: 16-byte aligned, so the band and general
-// kernels plan it as they plan an aligned destination.
-int64_t scratch_stride(const mxd_image& im) { return ((int64_t)im.crop_w * im.channels + 15) & ~(int64_t)15; }
 
 }  // namespace
 
@@ -316,439 +309,52 @@ int release_descs(Workspace* ws, void* stream, bool hit) {
   return MXD_OK;
 }
 
-int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored, const mxd_out_format* fmt) {
+namespace {
+
+// The call as a whole.  *out_dtype becomes the form the kernels are planned in.
+int validate_batch(const mxd_image* images, int32_t n, int32_t* out_dtype, int32_t device, const mxd_out_format* fmt) {
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
-  if (fmt) out_dtype = MXD_U8;  // the form the kernels of a formatted call are planned in
-  if (out_dtype != MXD_U8 && out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
+  if (fmt) *out_dtype = MXD_U8;  // the form the kernels of a formatted call are planned in
+  if (*out_dtype != MXD_U8 && *out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
   if (n == 0) return MXD_OK;
-  const int64_t elem = out_dtype == MXD_F32_DIV255 ? 4 : 1;
-  const int32_t channels = images[0].channels;
-  bool mixed = false;
+  const int64_t elem = *out_dtype == MXD_F32_DIV255 ? 4 : 1;
   for (int32_t i = 0; i < n; i++) {
     if (int rc = validate(images[i], i)) return rc;
-    mixed = mixed || images[i].channels != channels;
     if (!fmt && images[i].dst_stride < (int64_t)images[i].crop_w * images[i].channels * elem)
       return fail(MXD_ERR_INVALID, "mxd: dst_stride smaller than an output row");
   }
   if (fmt)
     if (int rc = fmt_validate_images(images, n, *fmt)) return rc;
-  if (int rc = check_device(device)) return rc;
-  if (mixed) {
-    // one channel count per launch: one sub-batch per count, in order
-    for (int32_t c = 1; c <= 4; c++) {
-      std::vector<mxd_image> sub;
-      std::vector<Stored> ssub;
-      for (int32_t i = 0; i < n; i++)
-        if (images[i].channels == c) {
-          sub.push_back(images[i]);
-          if (stored) ssub.push_back(stored[i]);
-        }
-      if (!sub.empty())
-        if (int rc = run_batch(sub.data(), (int32_t)sub.size(), out_dtype, device, stream, stored ? ssub.data() : nullptr,
-                               fmt))
-          return rc;
-    }
-    return MXD_OK;
-  }
-  if (channels == 4) {
-    // one alpha mode per general-kernel launch: split a mixed batch
-    int32_t nw = 0;
-    for (int32_t i = 0; i < n; i++) nw += images[i].rgba_weighted ? 1 : 0;
-    if (nw > 0 && nw < n) {
-      std::vector<mxd_image> a, b;
-      std::vector<Stored> sa, sb;
-      for (int32_t i = 0; i < n; i++) {
-        (images[i].rgba_weighted ? a : b).push_back(images[i]);
-        if (stored) (images[i].rgba_weighted ? sa : sb).push_back(stored[i]);
-      }
-      if (int rc = run_batch(a.data(), (int32_t)a.size(), out_dtype, device, stream, stored ? sa.data() : nullptr, fmt))
-        return rc;
-      return run_batch(b.data(), (int32_t)b.size(), out_dtype, device, stream, stored ? sb.data() : nullptr, fmt);
-    }
-  }
-  // A formatted call plans its kernels as a u8 call does: the wave kernels
-  // exist in the same shapes in every output mode and write any element
-  // alignment, and an image they do not take is resized into u8 scratch rows
-  // (16-byte aligned; their address is set once the plans are known) and
-  // formatted by a second launch.  From here on `images` is a copy whose
-  // destinations are those the resize kernels write.
-  std::vector<mxd_image> fmt_imgs;
-  const mxd_image* const callers = images;
-  if (fmt) {
-    fmt_imgs.assign(images, images + n);
-    for (mxd_image& im : fmt_imgs) {
-      im.dst = reinterpret_cast<void*>((uintptr_t)4096);
-      im.dst_stride = scratch_stride(im);
-    }
-    images = fmt_imgs.data();
-  }
-  const int32_t f32 = out_dtype == MXD_F32_DIV255 ? 1 : 0;
-  const bool no_wave = (g_policy.load() & MXD_POLICY_NO_WAVE) != 0;
-  std::vector<ImgPlan> plans(n);
-  std::vector<int32_t> slow;  // images for the general kernel
-  // Images of one geometry, layout and alignment share a plan (and later a
-  // schedule): planning walks tap tables, and a batch rarely holds more than
-  // a few shapes.  rep[i] = the first image with image i's key.
-  std::vector<int32_t> rep(n);
-  {
-    std::unordered_map<PlanKey, int32_t, PlanKeyHash> first_of;
-    first_of.reserve(16);
-    for (int32_t i = 0; i < n; i++) {
-      const mxd_image& im = images[i];
-      const Stored st = stored ? stored[i] : whole(im);
-      const auto ins = first_of.emplace(plan_key(im, st), i);
-      rep[i] = ins.first->second;
-      ImgPlan& p = plans[i];
-      if (!ins.second) {
-        p = plans[rep[i]];
-      } else {
-        if (int rc = tables().get(device, im.src_w, im.resize_w, &p.xt)) return rc;
-        if (int rc = tables().get(device, im.src_h, im.resize_h, &p.yt)) return rc;
-        if (st.ycc) {
-          // JPEG planes (the host path checked ycc_plan_ok): a wave kernel or nothing
-          plan_wave(im, st, f32, out_dtype, p);
-          if (!p.wave) return fail(MXD_ERR_UNSUPPORTED, "mxd: no wave kernel for a JPEG plane source");
-        } else if (!no_wave) {
-          if (g_policy.load() & MXD_POLICY_PREFER_BAND) {
-            plan_band(im, st, f32, p);
-            if (!p.band) plan_wave(im, st, f32, out_dtype, p);
-          } else {
-            plan_wave(im, st, f32, out_dtype, p);
-            if (!p.wave) plan_band(im, st, f32, p);
-          }
-        }
-      }
-      if (!p.band && !p.wave) slow.push_back(i);
-    }
-  }
-  DeviceGuard guard(device);
-  // Formatted call: the wave images' destinations are the caller's; the
-  // others get their scratch rows, and an entry for format_rows.
-  mxd::OutFmtDev ofd{};
-  std::vector<mxd::FmtRowDev> fmt_rows;
-  int32_t fmt_blocks = 0;
-  std::unique_lock<std::mutex> scratch_hold;
-  if (fmt) {
-    ofd.plane_stride = fmt->plane_stride;
-    ofd.elem16 = fmt_elem_size(*fmt) == 2 ? 1 : 0;
-    ofd.chw = fmt->layout == MXD_LAYOUT_CHW ? 1 : 0;
-    if (int rc = fmt_device_table(device, *fmt, channels, &ofd.table)) return rc;
-    size_t need = 0;
-    for (int32_t i = 0; i < n; i++)
-      if (!plans[i].wave) need += (size_t)(scratch_stride(images[i]) * images[i].crop_h + 255) & ~(size_t)255;
-    FmtScratch* sc = nullptr;
-    if (need > 0) {
-      sc = fmt_scratch(device, stream);
-      scratch_hold = std::unique_lock<std::mutex>(sc->mu);
-      if (int rc = grow_scratch(sc, need, stream)) return rc;
-    }
-    size_t at = 0;
-    for (int32_t i = 0; i < n; i++) {
-      mxd_image& im = fmt_imgs[i];
-      if (plans[i].wave) {
-        im.dst = callers[i].dst;
-        im.dst_stride = callers[i].dst_stride;
-        continue;
-      }
-      im.dst = sc->ptr + at;
-      at += (size_t)(im.dst_stride * im.crop_h + 255) & ~(size_t)255;
-      fmt_rows.push_back(mxd::FmtRowDev{static_cast<const uint8_t*>(im.dst), callers[i].dst, im.dst_stride,
-                                        callers[i].dst_stride, im.crop_w, im.crop_h, im.channels, fmt_blocks});
-      fmt_blocks += (im.crop_h + mxd::kFmtRows - 1) / mxd::kFmtRows;
-    }
-  }
-  auto fill = [&](ImgDev& d, int32_t i, const ImgPlan& p) {
-    const mxd_image& im = images[i];
-    const Stored st = stored ? stored[i] : whole(im);
-    d = ImgDev{};
-    d.src = st.base;
-    d.src_stride = st.stride;
-    d.src_w = im.src_w;
-    d.src_h = st.rows;
-    d.src_x0 = st.x0;
-    d.src_y0 = st.y0;
-    d.dst = im.dst;
-    d.dst_stride = im.dst_stride;
-    d.xwidth = p.xt->padded;
-    d.ywidth = p.yt->padded;
-    d.xtab = p.xt->ptr + (size_t)im.crop_x * (mxd::kTapHeader + p.xt->padded);
-    d.ytab = p.yt->ptr + (size_t)im.crop_y * (mxd::kTapHeader + p.yt->padded);
-    d.crop_w = im.crop_w;
-    d.crop_h = im.crop_h;
-    d.flip = im.flip ? 1 : 0;
-    d.ycc = st.ycc;
-  };
+  return check_device(device);
+}
 
-  // Descriptors of one upload: band-kernel images first, then wave-kernel
-  // images, then the general kernel's.
-  std::vector<ImgDev> descs(n);
+// Formatted call: the format as the kernels see it and, when some image takes
+// two passes, the stream's scratch (held until the last launch is enqueued)
+// with the layout's scratch offsets made addresses in it.
+int take_scratch(BatchLayout& L, const mxd_out_format& fmt, int32_t device, void* stream, mxd::OutFmtDev* ofd,
+                 std::unique_lock<std::mutex>* hold) {
+  ofd->plane_stride = fmt.plane_stride;
+  ofd->elem16 = fmt_elem_size(fmt) == 2 ? 1 : 0;
+  ofd->chw = fmt.layout == MXD_LAYOUT_CHW ? 1 : 0;
+  if (int rc = fmt_device_table(device, fmt, L.images[0].channels, &ofd->table)) return rc;
+  if (L.scratch_bytes == 0) return MXD_OK;
+  FmtScratch* sc = fmt_scratch(device, stream);
+  *hold = std::unique_lock<std::mutex>(sc->mu);
+  if (int rc = grow_scratch(sc, L.scratch_bytes, stream)) return rc;
+  L.add_scratch(sc->ptr);
+  return MXD_OK;
+}
 
-  // Band launches: one per (class, window KiB, lookahead).
-  auto bkey = [&](int32_t i) {
-    const mxd::BandPlan& b = plans[i].bp;
-    return std::make_tuple(b.cls, b.nq, b.la);
-  };
-  std::vector<int32_t> border;
-  for (int32_t i = 0; i < n; i++)
-    if (plans[i].band) border.push_back(i);
-  std::stable_sort(border.begin(), border.end(), [&](int32_t a, int32_t b) { return bkey(a) < bkey(b); });
-  const int32_t nbd = (int32_t)border.size();
-  struct BandGroup {
-    int32_t first, count, units;
-    mxd::BandCfg cfg;
-    int32_t table = -1;  // descriptor slot of the unit -> image table (per_img == 0)
-  };
-  std::vector<BandGroup> bgroups;
-  for (int32_t k = 0; k < nbd; k++) {
-    const mxd::BandPlan& b = plans[border[k]].bp;
-    if (bgroups.empty() || bkey(border[bgroups.back().first]) != bkey(border[k]))
-      bgroups.push_back({k, 0, 0, mxd::BandCfg{channels, f32, b.nq, b.taps, b.s, b.db, b.la, 0, 0, 0, 0}});
-    bgroups.back().count++;
-  }
-  for (BandGroup& g : bgroups) {
-    g.cfg.nimgs = g.count;
-    std::vector<std::pair<int32_t, int32_t>> strips;  // (nstrips, crop_h) per image
-    for (int32_t k = g.first; k < g.first + g.count; k++)
-      strips.push_back({plans[border[k]].bp.nstrips, images[border[k]].crop_h});
-    const int32_t forced = g_tune[MXD_TUNE_BAND_ROWS].load();
-    const int32_t capacity = band_capacity_cached(g.cfg, device);
-    const int32_t ty = forced > 0 ? forced : band_rows(strips, capacity, kBandMaxRows);
-    std::unordered_map<int32_t, const DevSched*> sched_of;  // by rep[] (one geometry, one band height)
-    for (int32_t k = g.first; k < g.first + g.count; k++) {
-      const int32_t i = border[k];
-      const mxd_image& im = images[i];
-      const ImgPlan& p = plans[i];
-      ImgDev& d = descs[k];
-      fill(d, i, p);
-      const uintptr_t a = reinterpret_cast<uintptr_t>(d.src);
-      d.src = reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)3);
-      d.flip |= (int32_t)(a & 3) << 8;
-      d.ty = std::min(ty, im.crop_h);
-      const DevSched*& sc = sched_of[rep[i]];
-      if (!sc)
-        if (int rc = band_schedule_dev(device, *p.yt, im.src_h, im.resize_h, im.crop_y, im.crop_h, d.ty, p.bp.db,
-                                          p.bp.s, p.bp.la + 2, &sc))
-          return rc;
-      d.ytab = reinterpret_cast<const float*>(sc->ptr);
-      d.ywidth = sc->band_words;
-      d.group = 0;
-      d.tile_begin = g.units;
-      d.nstrips = p.bp.nstrips;
-      d.tx = p.bp.tx;
-      const int32_t u = d.nstrips * ((im.crop_h + d.ty - 1) / d.ty);
-      g.cfg.per_img = k == g.first ? u : (g.cfg.per_img == u ? u : 0);
-      g.units += u;
-    }
-    g.cfg.nunits = g.units;
-    // A persistent grid: as many workgroups as the device holds at once,
-    // each running an equal share of units (measured on C2 / 12 MP / 24 MP:
-    // 0.158 / 0.195 / 0.367 ms against 0.17-0.19 / 0.224 / 0.383 with one
-    // workgroup per unit); MXD_TUNE_BAND_GRID overrides.
-    const int32_t knob = g_tune[MXD_TUNE_BAND_GRID].load();
-    int32_t grid = knob == 1 ? g.units : knob > 1 ? knob : (capacity > 0 ? capacity : 1024);
-    grid = std::max(1, std::min(g.units, grid));
-    g.cfg.grid = (g.units + (g.units + grid - 1) / grid - 1) / ((g.units + grid - 1) / grid);
-  }
-  // Unit -> image tables of the band launches whose images differ in unit
-  // count, after every descriptor (ImgDev-sized blocks of int32).
-  std::vector<int32_t> unit_tables;
-  for (BandGroup& g : bgroups) {
-    if (g.cfg.per_img > 0) continue;
-    g.table = (int32_t)unit_tables.size();
-    for (int32_t k = g.first; k < g.first + g.count; k++) {
-      const ImgDev& d = descs[k];
-      const int32_t u = d.nstrips * ((images[border[k]].crop_h + d.ty - 1) / d.ty);
-      unit_tables.insert(unit_tables.end(), u, k - g.first);
-    }
-    unit_tables.resize((unit_tables.size() * 4 + sizeof(ImgDev) - 1) / sizeof(ImgDev) * sizeof(ImgDev) / 4, 0);
-  }
-
-  // Wave launches: one per kernel (kind, tap bucket, scatter shape, q,
-  // shift).
-  auto key = [&](int32_t i) {
-    const ImgPlan& p = plans[i];
-    return std::make_tuple(p.kind, p.bucket, p.s, p.dmax, p.q, p.shift, p.pp, p.ycc);
-  };
-  std::vector<int32_t> order;
-  for (int32_t i = 0; i < n; i++)
-    if (plans[i].wave) order.push_back(i);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key(a) < key(b); });
-  const int32_t nw = (int32_t)order.size();
-  const int32_t wbase = nbd;  // first wave descriptor
-  struct Group {
-    int32_t first, count, units, ty;
-    mxd::WaveCfg cfg;
-  };
-  std::vector<Group> groups;
-  for (int32_t k = 0; k < nw; k++) {
-    const ImgPlan& p = plans[order[k]];
-    if (groups.empty() || key(order[groups.back().first]) != key(order[k]))
-      groups.push_back(
-          {k, 0, 0, 0, mxd::WaveCfg{channels, fmt ? mxd::kWaveOutFmt : f32, p.bucket, 0, 0, p.kind, p.s, p.dmax, p.q,
-                                    p.shift, p.pp, 0, 1, p.ycc ? 1 : 0}});
-    groups.back().count++;
-  }
-  // Source load policy (wave.hip LAUX): streaming (nt) loads when the
-  // call's sources are far past what the 256 MB Infinity Cache could hold
-  // for a re-read (sources just written by a decode or a copy stay there,
-  // and nt loads would bypass them: C4's 128 small images measured 45 %
-  // slower with nt, C2 / C3 / C5 2-7 % faster; profiles/r06/README.md).
-  // MXD_TUNE_LOAD_POLICY: 1 = default policy always, 2 = nt always.
-  int64_t src_bytes = 0;
-  for (int32_t i : order) src_bytes += (int64_t)images[i].src_w * images[i].src_h * images[i].channels;
-  const int32_t load_knob = g_tune[MXD_TUNE_LOAD_POLICY].load();
-  const int32_t nt = load_knob == 2 ? 1 : load_knob == 1 ? 0 : src_bytes >= kNtSourceBytes ? 1 : 0;
-  for (Group& g : groups) {
-    g.cfg.nimgs = g.count;
-    g.cfg.nt = g.cfg.ycc ? 0 : nt;
-    std::vector<std::pair<int32_t, int32_t>> strips;  // (nstrips, crop_h) per image
-    for (int32_t k = g.first; k < g.first + g.count; k++) strips.push_back({plans[order[k]].nstrips, images[order[k]].crop_h});
-    g.ty = band_rows(strips, wave_capacity_cached(g.cfg, device));
-    std::unordered_map<int32_t, const DevSched*> sched_of;  // by rep[]
-    for (int32_t k = g.first; k < g.first + g.count; k++) {
-      const int32_t i = order[k];
-      const mxd_image& im = images[i];
-      const ImgPlan& p = plans[i];
-      ImgDev& d = descs[wbase + k];
-      fill(d, i, p);
-      // aligned base + byte shift (ImgDev::flip bits 8..)
-      const uintptr_t a = reinterpret_cast<uintptr_t>(d.src);
-      d.src = reinterpret_cast<const uint8_t*>(a & ~(uintptr_t)3);
-      d.flip |= (int32_t)(a & 3) << 8;
-      d.ty = std::min(g.ty, im.crop_h);
-      if (p.kind == 2) {
-        const DevSched*& sc = sched_of[rep[i]];
-        if (!sc)
-          if (int rc = scatter_schedule(device, *p.yt, im.src_h, im.resize_h, im.crop_y, im.crop_h, d.ty,
-                                       ScatterShape{p.s, p.dmax, p.p,
-                                                    p.ycc ? mxd::kYccLaneBytes : p.pp == 16 ? 16 : p.pp * channels},
-                                       &sc))
-            return rc;
-        d.ytab = reinterpret_cast<const float*>(sc->ptr);
-        d.ywidth = sc->band_words;
-        d.group = sc->entry_off;
-      } else {
-        d.group = 1;
-      }
-      d.tile_begin = g.units;
-      d.nstrips = p.nstrips;
-      d.tx = p.tx;
-      const int32_t u = d.nstrips * ((im.crop_h + d.ty - 1) / d.ty);
-      g.cfg.per_img = k == g.first ? u : (g.cfg.per_img == u ? u : 0);
-      g.units += u;
-    }
-    g.cfg.nunits = g.units;
-  }
-
-  // General path (any alignment, any tap count): workgroup tiles, resample.hip.
-  LaunchCfg cfg{};
-  int32_t tiles = 0;
-  if (!slow.empty()) {
-    // The tile kernel addresses rows from the image's row 0: a staged
-    // footprint is reached through the (never dereferenced) address its
-    // row 0 would have; the kernel only reads footprint rows and columns.
-    auto base0 = [&](int32_t i) {
-      const Stored st = stored ? stored[i] : whole(images[i]);
-      return st.base - (int64_t)st.y0 * st.stride - (int64_t)st.x0 * images[i].channels;
-    };
-    bool aligned16 = true;
-    for (int32_t i : slow) {
-      const Stored st = stored ? stored[i] : whole(images[i]);
-      const uintptr_t a = reinterpret_cast<uintptr_t>(base0(i)) | (uintptr_t)st.stride;
-      aligned16 = aligned16 && (a & 15) == 0;
-    }
-    const int32_t vec = aligned16 ? 16 : 1;
-    cfg.vec = vec;
-    cfg.channels = channels;
-    cfg.alpha = channels == 4 && images[slow[0]].rgba_weighted ? 1 : 0;
-    cfg.f32 = f32;
-    cfg.nimgs = (int32_t)slow.size();
-    for (size_t k = 0; k < slow.size(); k++) {
-      const int32_t i = slow[k];
-      const mxd_image& im = images[i];
-      const DevTable* xt = plans[i].xt;
-      const DevTable* yt = plans[i].yt;
-      const bool flip = im.flip != 0;
-      // Column strips: enough that one strip row's footprint is ~kStripBytes.
-      const int32_t full = strip_chunks(*xt, im.crop_x, im.crop_w, 0, im.crop_w, flip, channels, 1);
-      int32_t nstrips = std::max<int32_t>(1, (full + kStripBytes - 1) / kStripBytes);
-      int32_t tx = (im.crop_w + nstrips - 1) / nstrips;
-      tx = std::min<int32_t>(im.crop_w, (tx + 3) & ~3);
-      nstrips = (im.crop_w + tx - 1) / tx;
-      int32_t max_chunks = 0;
-      for (int32_t s = 0; s < nstrips; s++) {
-        const int32_t ox0 = s * tx, ox1 = std::min(ox0 + tx, im.crop_w);
-        max_chunks = std::max(max_chunks, strip_chunks(*xt, im.crop_x, im.crop_w, ox0, ox1, flip, channels, vec));
-      }
-      const int32_t vw = (max_chunks * vec + 3) & ~3;
-      const int32_t ty = std::min(kTileRows, im.crop_h);
-      int32_t group = std::max<int32_t>(1, std::min<int32_t>(8, 512 / std::max(1, max_chunks)));
-      group = std::max<int32_t>(1, std::min<int32_t>(group, kLdsBudget / (vw * 4)));
-      group = std::min(group, ty);
-      const int32_t nbands = (im.crop_h + ty - 1) / ty;
-      ImgDev& d = descs[wbase + nw + k];
-      fill(d, i, plans[i]);
-      d.src = base0(i);
-      d.src_h = im.src_h;
-      d.src_x0 = d.src_y0 = 0;
-      d.tile_begin = tiles;
-      d.nstrips = nstrips;
-      d.ty = ty;
-      d.tx = tx;
-      d.group = group;
-      tiles += nbands * nstrips;
-      cfg.max_tx = std::max(cfg.max_tx, tx);
-      cfg.max_ty = std::max(cfg.max_ty, ty);
-      cfg.max_xw = std::max(cfg.max_xw, xt->padded);
-      cfg.max_yw = std::max(cfg.max_yw, yt->padded);
-      cfg.max_vw = std::max(cfg.max_vw, vw);
-      cfg.max_group = std::max(cfg.max_group, group);
-    }
-    cfg.ntiles = tiles;
-    if (mxd::resample_smem_bytes(cfg) > 160 * 1024) return fail(MXD_ERR_UNSUPPORTED, "mxd: tile does not fit in LDS");
-  }
-
-  ImgDev* dev = nullptr;
-  std::unique_lock<std::mutex> hold;
-  Workspace* ws = nullptr;
-  bool hit = false;
-  if (!unit_tables.empty()) {
-    const size_t at = descs.size();
-    descs.resize(at + unit_tables.size() * 4 / sizeof(ImgDev));
-    std::memcpy(reinterpret_cast<void*>(descs.data() + at), unit_tables.data(), unit_tables.size() * 4);
-  }
-  // format_rows' entries after them (ImgDev-sized blocks as well): part of
-  // the slot's bytes, so a cached slot is reused only with the same scratch
-  // rows and destinations.  The format itself is a launch argument.
-  const size_t fmt_at = descs.size();
-  if (!fmt_rows.empty()) {
-    const size_t bytes = fmt_rows.size() * sizeof(mxd::FmtRowDev);
-    descs.resize(fmt_at + (bytes + sizeof(ImgDev) - 1) / sizeof(ImgDev));
-    std::memcpy(reinterpret_cast<void*>(descs.data() + fmt_at), fmt_rows.data(), bytes);
-  }
-  if (int rc = upload_descs(descs, device, stream, &dev, &hold, &ws, &hit)) return rc;
-  const int32_t* tables_dev = reinterpret_cast<const int32_t*>(dev + n);
-  // Several launches: fork them over the caller's stream and the workspace's
-  // helper streams (largest first), join back before return, so one launch's
-  // tail overlaps the next.
-  struct Launch {
-    int64_t units;
-    int32_t kind;   // 0 band, 1 wave, 2 general
-    int32_t group;
-  };
-  std::vector<Launch> launches;
-  // (a band unit is a workgroup, ~4 wave units)
-  for (size_t g = 0; g < bgroups.size(); g++) launches.push_back({4 * (int64_t)bgroups[g].units, 0, (int32_t)g});
-  for (size_t g = 0; g < groups.size(); g++) launches.push_back({groups[g].units, 1, (int32_t)g});
-  if (!slow.empty()) launches.push_back({tiles, 2, -1});
-  std::stable_sort(launches.begin(), launches.end(), [](const Launch& a, const Launch& b) { return a.units > b.units; });
+// Several launches: fork them over the caller's stream and the workspace's
+// helper streams (largest first), join back before return, so one launch's
+// tail overlaps the next.
+int launch_all(const BatchLayout& L, const ImgDev* dev, Workspace* ws, const mxd::OutFmtDev* ofd, void* stream) {
   // Streams: the caller's and one helper by default.  C3's six launches
   // measured 0.465 ms on one stream, 0.429 on two and 0.455 on four
   // (profiles/r03/c3_sizing.jsonl); MXD_TUNE_STREAMS overrides.
   const int32_t knob_streams = g_tune[MXD_TUNE_STREAMS].load();
   const int32_t nstreams = knob_streams > 0 ? knob_streams : 2;
-  const int nfork = std::min<int>({(int)launches.size() - 1, nstreams - 1, Workspace::kHelpers});
+  const int nfork = std::min<int>({(int)L.launches.size() - 1, nstreams - 1, Workspace::kHelpers});
   if (nfork > 0) {
     if (!ws->fork) {
       MXD_HIP(hipEventCreateWithFlags(&ws->fork, hipEventDisableTiming));
@@ -760,21 +366,22 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
     MXD_HIP(hipEventRecord(ws->fork, reinterpret_cast<hipStream_t>(stream)));
     for (int h = 0; h < nfork; h++) MXD_HIP(hipStreamWaitEvent(ws->helper[h], ws->fork, 0));
   }
+  const int32_t* tables_dev = reinterpret_cast<const int32_t*>(dev + L.tables_at);
   int launch_rc = MXD_OK;
-  for (size_t k = 0; k < launches.size(); k++) {
+  for (size_t k = 0; k < L.launches.size(); k++) {
     const int lane = nfork > 0 ? (int)(k % (size_t)(nfork + 1)) : 0;
     void* s = lane == 0 ? stream : reinterpret_cast<void*>(ws->helper[lane - 1]);
     int rc = 0;
-    if (launches[k].kind == 0) {
-      const BandGroup& g = bgroups[launches[k].group];
+    if (L.launches[k].kind == 0) {
+      const BatchLayout::BandGroup& g = L.bands[L.launches[k].group];
       rc = mxd::launch_band(g.cfg, dev + g.first, g.table >= 0 ? tables_dev + g.table : nullptr, s);
-    } else if (launches[k].kind == 1) {
-      Group& g = groups[launches[k].group];
-      g.cfg.prio = nfork == 0 ? 1 : 0;  // priorities only where launches never overlap
-      rc = fmt ? mxd::launch_wave_fmt(g.cfg, dev + wbase + g.first, ofd, s)
-               : mxd::launch_wave(g.cfg, dev + wbase + g.first, s);
+    } else if (L.launches[k].kind == 1) {
+      const BatchLayout::WaveGroup& g = L.waves[L.launches[k].group];
+      mxd::WaveCfg cfg = g.cfg;
+      cfg.prio = nfork == 0 ? 1 : 0;  // priorities only where launches never overlap
+      rc = ofd ? mxd::launch_wave_fmt(cfg, dev + g.first, *ofd, s) : mxd::launch_wave(cfg, dev + g.first, s);
     } else {
-      rc = mxd::launch_resample(cfg, dev + wbase + nw, s);
+      rc = mxd::launch_resample(L.general, dev + L.general_at, s);
     }
     if (rc) {
       launch_rc = fail(MXD_ERR_DEVICE, std::string("resample launch failed: ") + hipGetErrorString(hipGetLastError()) +
@@ -783,24 +390,73 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
     }
   }
   // Every helper stream that may hold kernels of this batch joins the
-  // caller's stream and the batch is counted -- on a failed launch too, so the
-  // slot's fence covers the kernels already queued and a caller syncing its
-  // own stream waits for their writes.
+  // caller's stream -- on a failed launch too, so the slot's fence covers the
+  // kernels already queued and a caller syncing its own stream waits for
+  // their writes.
   for (int h = 0; h < nfork; h++) {
     if (hipEventRecord(ws->join[h], ws->helper[h]) != hipSuccess ||
         hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), ws->join[h], 0) != hipSuccess)
       if (launch_rc == MXD_OK) launch_rc = fail(MXD_ERR_DEVICE, "mxd: joining helper streams failed");
   }
+  return launch_rc;
+}
+
+// One launchable batch: its layout, the upload, the launches.
+int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
+                   const Stored* stored, const mxd_out_format* fmt) {
+  DeviceGuard guard(device);
+  BatchLayout L;
+  if (int rc = build_layout(device_env(), device, images, n, stored, out_dtype, fmt, &L)) return rc;
+  mxd::OutFmtDev ofd{};
+  std::unique_lock<std::mutex> scratch_hold;
+  if (fmt)
+    if (int rc = take_scratch(L, *fmt, device, stream, &ofd, &scratch_hold)) return rc;
+  ImgDev* dev = nullptr;
+  std::unique_lock<std::mutex> hold;
+  Workspace* ws = nullptr;
+  bool hit = false;
+  if (int rc = upload_descs(L.descs, device, stream, &dev, &hold, &ws, &hit)) return rc;
+  int launch_rc = launch_all(L, dev, ws, fmt ? &ofd : nullptr, stream);
   // The second pass of a formatted call, behind the joins: every resize
   // kernel that wrote scratch rows is ordered before it on the caller's stream.
-  if (launch_rc == MXD_OK && !fmt_rows.empty() &&
-      mxd::launch_format_rows(reinterpret_cast<const mxd::FmtRowDev*>(dev + fmt_at), (int)fmt_rows.size(), fmt_blocks,
-                              ofd, stream))
+  if (launch_rc == MXD_OK && L.fmt_count > 0 &&
+      mxd::launch_format_rows(reinterpret_cast<const mxd::FmtRowDev*>(dev + L.fmt_at), L.fmt_count, L.fmt_blocks, ofd,
+                              stream))
     launch_rc = fail(MXD_ERR_DEVICE, std::string("format_rows launch failed: ") + hipGetErrorString(hipGetLastError()));
+  // The batch is counted on a failed launch too (see launch_all).
   const int rel = release_descs(ws, stream, hit);
   return launch_rc != MXD_OK ? launch_rc : rel;
 }
 
+}  // namespace
+
+// One channel count per launch, and one alpha mode per general-kernel launch.
+std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stored* stored) {
+  // launch classes in order: 1, 2, 3 channels, RGBA weighted, RGBA not (the flag means nothing below four channels)
+  auto cls = [](const mxd_image& im) { return 2 * im.channels - (im.channels == 4 && im.rgba_weighted ? 1 : 0); };
+  std::vector<SubBatch> subs;
+  bool mixed = false;
+  for (int32_t i = 1; i < n; i++) mixed = mixed || cls(images[i]) != cls(images[0]);
+  for (int32_t c = 2; mixed && c <= 8; c++) {
+    SubBatch s = partition(images, n, stored, [&](const mxd_image& im) { return cls(im) == c; });
+    if (!s.images.empty()) subs.push_back(std::move(s));
+  }
+  return subs;
+}
+
+int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
+              const Stored* stored, const mxd_out_format* fmt) {
+  if (int rc = validate_batch(images, n, &out_dtype, device, fmt)) return rc;
+  if (n == 0) return MXD_OK;
+  const std::vector<SubBatch> subs = split_batch(images, n, stored);
+  if (subs.empty()) return run_launchable(images, n, out_dtype, device, stream, stored, fmt);
+  for (const SubBatch& s : subs)
+    if (int rc = run_launchable(s.images.data(), (int32_t)s.images.size(), out_dtype, device, stream,
+                                stored ? s.stored.data() : nullptr, fmt))
+      return rc;
+  return MXD_OK;
+}
 
 }  // namespace capi
 }  // namespace mxd
+

@@ -255,8 +255,7 @@ int mxd_describe_band_plan(const mxd_image* image, int32_t out_dtype, int32_t* i
   ImgPlan p;
   if (int rc = host_tables().get(0, image->src_w, image->resize_w, &p.xt)) return rc;
   if (int rc = host_tables().get(0, image->src_h, image->resize_h, &p.yt)) return rc;
-  const int32_t f32 = out_dtype == MXD_F32_DIV255 ? 1 : 0;
-  plan_band(*image, whole(*image), f32, p);
+  plan_band(*image, whole(*image), out_dtype, p);
   const mxd::BandPlan& b = p.bp;
   mxd::BandCfg cfg{};
   cfg.nq = b.nq;
@@ -274,7 +273,7 @@ int mxd_describe_plan(const mxd_image* image, int32_t out_dtype, int32_t device,
   ImgPlan p;
   if (int rc = host_tables().get(device, image->src_w, image->resize_w, &p.xt)) return rc;
   if (int rc = host_tables().get(device, image->src_h, image->resize_h, &p.yt)) return rc;
-  if (!(g_policy.load() & MXD_POLICY_NO_WAVE)) plan_wave(*image, whole(*image), out_dtype == MXD_F32_DIV255, out_dtype, p);
+  if (!(g_policy.load() & MXD_POLICY_NO_WAVE)) plan_wave(*image, whole(*image), out_dtype, p);
   const int32_t v[8] = {p.wave ? 1 : 0, p.kind, p.bucket, p.s, p.dmax, p.q, p.nstrips, p.pp};
   std::memcpy(info8, v, sizeof v);
   return MXD_OK;

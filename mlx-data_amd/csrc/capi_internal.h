@@ -1,14 +1,17 @@
 // capi_internal.h -- what the translation units of the C ABI share:
 // capi.cpp (extern "C" entry points, pixel maps, process-wide state),
-// plan.cpp (tap tables, kernel planning, schedule caches), batch.cpp
-// (descriptor workspaces, run_batch: one fused launch per kernel shape) and
-// hostpath.cpp / hostjpeg.cpp (host-resident and JPEG batches staged through
+// plan.cpp (tap tables, kernel planning, the schedule cache),
+// batch_layout.cpp (build_layout: a batch's descriptors, launch groups and
+// launch order, built without a device), batch.cpp (descriptor workspaces,
+// run_batch: uploads a layout and launches it, one fused launch per kernel
+// shape) and hostpath.cpp / hostjpeg.cpp (host-resident and JPEG batches staged through
 // page-locked memory; hostpath.h).  Host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sched.h>
 
 #include <algorithm>
+#include <array>
 #include <numeric>
 #include <atomic>
 #include <cmath>
@@ -174,19 +177,29 @@ struct ScatterShape {
 };
 ScatterShape scatter_shape(const DevTable& t, int32_t off, int32_t len);
 
-// Scatter schedules (layout: wave.hip) in device memory, one per
-// (device, vertical geometry, crop rows, band height, shape).
+// The wave kernels' scatter schedule (layout: wave.hip) for crop rows
+// [crop_y, crop_y + crop_h) in bands of ty rows: `band_words` words per band,
+// the iteration entries `entry_off` words into each.  Returns false if the
+// rows do not fit the shape.  (The band kernel's: band_plan.h band_schedule.)
+bool scatter_schedule_words(const DevTable& yt, int32_t crop_y, int32_t crop_h, int32_t ty, const ScatterShape& sh,
+                            std::vector<int32_t>* words, int32_t* band_words, int32_t* entry_off);
+
+// A schedule in device memory.
 struct DevSched {
   int32_t* ptr = nullptr;
   int32_t band_words = 0;  // words per band
-  int32_t entry_off = 0;   // word offset of the iteration entries in a band
+  int32_t entry_off = 0;   // word offset of the iteration entries in a band (band kernel: 0)
 };
-// Device copies of the wave kernels' scatter schedule and of the band
-// kernel's schedule, built once per geometry and cached.
-int scatter_schedule(int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h, int32_t crop_y,
-                     int32_t crop_h, int32_t ty, const ScatterShape& sh, const DevSched** out);
-int band_schedule_dev(int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h, int32_t crop_y, int32_t crop_h,
-                  int32_t ty, int32_t db, int32_t s, int32_t min_groups, const DevSched** out);
+// Both kernels' schedules, built once per (kind, device, vertical geometry,
+// crop rows, band height, shape or class) and cached (plan.cpp).
+class SchedCache;
+SchedCache& schedules();
+SchedCache& host_schedules();  // built and checked but never uploaded (ptr stays null)
+int scatter_schedule(SchedCache& cache, int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h,
+                     int32_t crop_y, int32_t crop_h, int32_t ty, const ScatterShape& sh, const DevSched** out);
+int band_schedule_dev(SchedCache& cache, int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h,
+                      int32_t crop_y, int32_t crop_h, int32_t ty, int32_t db, int32_t s, int32_t min_groups,
+                      const DevSched** out);
 mxd::AxisView axis_view(const DevTable& t);
 
 bool wave_strips(const DevTable& xt, const mxd_image& im, int32_t pp, int32_t* nstrips, int32_t* tx, int32_t* q);
@@ -208,8 +221,8 @@ struct Stored {
 
 Stored whole(const mxd_image& im);
 bool wave_layout_ok(const mxd_image& im, const Stored& st, int32_t out_dtype);
-void plan_band(const mxd_image& im, const Stored& st, int32_t f32, ImgPlan& p);
-void plan_wave(const mxd_image& im, const Stored& st, int32_t f32, int32_t out_dtype, ImgPlan& p);
+void plan_band(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan& p);
+void plan_wave(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan& p);
 // Whether run_batch would resize image im from the JPEG planes st.ycc
 // describes (a scatter wave kernel with RGB pixel lanes takes it).
 bool ycc_plan_ok(const mxd_image& im, const Stored& st, int32_t out_dtype, int32_t device);
@@ -230,8 +243,86 @@ struct PlanKeyHash {
 PlanKey plan_key(const mxd_image& im, const Stored& st);
 
 // ---------------------------------------------------------------------------
+// Batch layout (batch_layout.cpp): what one launchable batch (one channel
+// count, one alpha mode) uploads and launches, as a plain value.  Building it
+// makes no device call of its own: what it needs from a device reaches it
+// through a LayoutEnv, whose host form (host_env) plans without one.  There
+// the device pointers in the descriptors are null plus their offsets;
+// everything else is what the device form builds.
+struct LayoutEnv {
+  TableCache* tables;
+  SchedCache* scheds;
+  int32_t band_capacity, wave_capacity;  // workgroups / waves the device runs at once; < 0: ask the device
+};
+LayoutEnv device_env();
+LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
+
+struct BatchLayout {
+  struct BandGroup {
+    int32_t first, count, units;  // first descriptor, images, units
+    mxd::BandCfg cfg;
+    int32_t table = -1;  // word offset of its unit -> image table among the tables (per_img == 0)
+  };
+  struct WaveGroup {
+    int32_t first, count, units, ty;
+    mxd::WaveCfg cfg;
+  };
+  struct Launch {
+    int64_t units;  // a band unit (a workgroup) counts as 4 wave units
+    int32_t kind;   // 0 band, 1 wave, 2 general
+    int32_t group;
+  };
+  int32_t n = 0;
+  std::vector<ImgPlan> plans;     // by batch index
+  std::vector<int32_t> image_of;  // batch index of descriptor k < n: band, then wave, then general images
+  // One upload, in ImgDev-sized blocks: the n descriptors, the unit -> image
+  // tables from tables_at, format_rows' entries from fmt_at.
+  std::vector<ImgDev> descs;
+  size_t tables_at = 0, fmt_at = 0;
+  std::vector<BandGroup> bands;
+  std::vector<WaveGroup> waves;
+  int32_t general_at = 0;  // first descriptor of the general kernel
+  LaunchCfg general{};     // nimgs == 0: no general launch
+  std::vector<Launch> launches;  // largest first
+  // Formatted call: images no wave kernel takes are resized into u8 scratch
+  // rows and formatted by format_rows.  Their descriptors' dst and their
+  // entries' src are offsets into a scratch of scratch_bytes (add_scratch).
+  std::vector<mxd_image> images;  // the batch with the destinations the resize kernels write
+  size_t scratch_bytes = 0;
+  int32_t fmt_count = 0, fmt_blocks = 0;
+  mxd::FmtRowDev* fmt_rows() { return reinterpret_cast<mxd::FmtRowDev*>(descs.data() + fmt_at); }
+  const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
+  void add_scratch(uint8_t* base);
+};
+// fmt != nullptr: a formatted call (out_dtype is not read; the format's values
+// are launch arguments, not part of the layout).
+int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
+                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out);
+
+// The images of a batch for which pred holds, in batch order, with their
+// stored entries.
+struct SubBatch {
+  std::vector<mxd_image> images;
+  std::vector<Stored> stored;
+};
+template <class Pred>
+SubBatch partition(const mxd_image* images, int32_t n, const Stored* stored, Pred pred) {
+  SubBatch s;
+  for (int32_t i = 0; i < n; i++)
+    if (pred(images[i])) {
+      s.images.push_back(images[i]);
+      if (stored) s.stored.push_back(stored[i]);
+    }
+  return s;
+}
+// The launchable sub-batches of a batch, in launch order: by channel count,
+// RGBA with weighted alpha first.  Empty: the batch is launchable as it is.
+std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stored* stored);
+
+// ---------------------------------------------------------------------------
 // Batches (batch.cpp): one fused launch per kernel shape over a batch whose
-// sources are in device memory (or, from the host path, staged: stored[i]).
+// sources are in device memory (or, from the host path, staged: stored[i]):
+// validation, split_batch, build_layout, then upload and launches.
 // fmt != nullptr: a formatted output (out_dtype is not read).  Images a wave
 // kernel takes are written in that form by the resize launch; the others are
 // resized into a per-(device, stream) u8 scratch and formatted by one

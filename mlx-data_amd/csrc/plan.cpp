@@ -60,99 +60,65 @@ ScatterShape scatter_shape(const DevTable& t, int32_t off, int32_t len) {
 }
 
 
-class SchedCache {
- public:
-  int get(int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h, int32_t crop_y, int32_t crop_h,
-          int32_t ty, const ScatterShape& sh, const DevSched** out) {
-    std::lock_guard<std::mutex> lock(mu_);
-    const auto key = std::make_tuple(device, src_h, resize_h, crop_y, crop_h, ty, sh.s, sh.dmax, sh.p, sh.lane_bytes);
-    auto it = map_.find(key);
-    if (it != map_.end()) {
-      *out = it->second.get();
-      return MXD_OK;
-    }
-    auto sched = std::make_unique<DevSched>();
-    std::vector<int32_t> words;
-    if (!build(yt, crop_y, crop_h, ty, sh, &words, sched.get()))
-      return fail(MXD_ERR_INVALID, "mxd: scatter schedule does not fit its shape");
-    DeviceGuard g(device);
-    MXD_HIP(hipMalloc(reinterpret_cast<void**>(&sched->ptr), words.size() * sizeof(int32_t)));
-    MXD_HIP(hipMemcpy(sched->ptr, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    *out = sched.get();
-    map_[key] = std::move(sched);
-    return MXD_OK;
+bool scatter_schedule_words(const DevTable& yt, int32_t crop_y, int32_t crop_h, int32_t ty, const ScatterShape& sh,
+                            std::vector<int32_t>* words, int32_t* band_words, int32_t* entry_off) {
+  const int32_t S = sh.s, D = sh.dmax, P = sh.p;
+  const int32_t la = mxd::scatter_ring_slots(D, sh.lane_bytes) - 1,
+                bg = mxd::scatter_block_groups(S, D, sh.lane_bytes);
+  const int32_t E = mxd::scatter_entry_words(S);
+  const int32_t nb = (crop_h + ty - 1) / ty;
+  const int32_t gmax = (P + ty + bg - 1) / bg * bg;
+  const int32_t gwords = (1 + gmax + 3) & ~3;
+  const int32_t iters = gmax * D + la;
+  *band_words = gwords + iters * E;
+  *entry_off = gwords;
+  words->assign((size_t)nb * *band_words, 0);
+  auto first = [&](int32_t y) { return yt.first[crop_y + y]; };
+  auto last = [&](int32_t y) { return yt.first[crop_y + y] + yt.count[crop_y + y] - 1; };
+  for (int32_t b = 0; b < nb; b++) {
+    int32_t* w = words->data() + (size_t)b * *band_words;
+    const int32_t y0 = b * ty, n = std::min(ty, crop_h - y0);
+    w[0] = (P + n + bg - 1) / bg * bg;
+    for (int32_t g = 0; g < gmax; g++) w[1 + g] = g >= P && g - P < n ? y0 + g - P : -1;
+    int32_t* ent = w + gwords;
+    for (int32_t i = 0; i < iters; i++) ent[i * E] = ent[i * E + 1] = -1;
+    std::vector<int32_t> fill(gmax, 0);
+    bool ok = true;
+    auto add_row = [&](int32_t g, int32_t r) {
+      if (g < 0 || g >= gmax || fill[g] >= D) return void(ok = false);
+      int32_t* e = ent + (size_t)(g * D + fill[g]++) * E;
+      e[1] = r;
+      for (int32_t u = 0; u < n; u++) {
+        if (r < first(y0 + u) || r > last(y0 + u)) continue;
+        const int32_t k = P + u - g;
+        if (k < 0 || k >= S) return void(ok = false);
+        const float wt = yt.w[(size_t)(crop_y + y0 + u) * yt.width + (r - first(y0 + u))];
+        std::memcpy(&e[2 + k], &wt, sizeof(float));
+      }
+    };
+    for (int32_t r = first(y0); r <= last(y0); r++) add_row(P - (last(y0) - r) / D, r);
+    for (int32_t u = 1; u < n; u++)
+      for (int32_t r = last(y0 + u - 1) + 1; r <= last(y0 + u); r++) add_row(P + u, r);
+    if (!ok) return false;
+    // word 0 of iteration i: the row iteration i + la loads into the ring
+    for (int32_t i = 0; i + la < iters; i++) ent[i * E] = ent[(i + la) * E + 1];
   }
-
- private:
-  static bool build(const DevTable& yt, int32_t crop_y, int32_t crop_h, int32_t ty, const ScatterShape& sh,
-                    std::vector<int32_t>* words, DevSched* d) {
-    const int32_t S = sh.s, D = sh.dmax, P = sh.p;
-    const int32_t la = mxd::scatter_ring_slots(D, sh.lane_bytes) - 1,
-                  bg = mxd::scatter_block_groups(S, D, sh.lane_bytes);
-    const int32_t E = mxd::scatter_entry_words(S);
-    const int32_t nb = (crop_h + ty - 1) / ty;
-    const int32_t gmax = (P + ty + bg - 1) / bg * bg;
-    const int32_t gwords = (1 + gmax + 3) & ~3;
-    const int32_t iters = gmax * D + la;
-    d->band_words = gwords + iters * E;
-    d->entry_off = gwords;
-    words->assign((size_t)nb * d->band_words, 0);
-    auto first = [&](int32_t y) { return yt.first[crop_y + y]; };
-    auto last = [&](int32_t y) { return yt.first[crop_y + y] + yt.count[crop_y + y] - 1; };
-    for (int32_t b = 0; b < nb; b++) {
-      int32_t* w = words->data() + (size_t)b * d->band_words;
-      const int32_t y0 = b * ty, n = std::min(ty, crop_h - y0);
-      w[0] = (P + n + bg - 1) / bg * bg;
-      for (int32_t g = 0; g < gmax; g++) w[1 + g] = g >= P && g - P < n ? y0 + g - P : -1;
-      int32_t* ent = w + gwords;
-      for (int32_t i = 0; i < iters; i++) ent[i * E] = ent[i * E + 1] = -1;
-      std::vector<int32_t> fill(gmax, 0);
-      bool ok = true;
-      auto add_row = [&](int32_t g, int32_t r) {
-        if (g < 0 || g >= gmax || fill[g] >= D) return void(ok = false);
-        int32_t* e = ent + (size_t)(g * D + fill[g]++) * E;
-        e[1] = r;
-        for (int32_t u = 0; u < n; u++) {
-          if (r < first(y0 + u) || r > last(y0 + u)) continue;
-          const int32_t k = P + u - g;
-          if (k < 0 || k >= S) return void(ok = false);
-          const float wt = yt.w[(size_t)(crop_y + y0 + u) * yt.width + (r - first(y0 + u))];
-          std::memcpy(&e[2 + k], &wt, sizeof(float));
-        }
-      };
-      for (int32_t r = first(y0); r <= last(y0); r++) add_row(P - (last(y0) - r) / D, r);
-      for (int32_t u = 1; u < n; u++)
-        for (int32_t r = last(y0 + u - 1) + 1; r <= last(y0 + u); r++) add_row(P + u, r);
-      if (!ok) return false;
-      // word 0 of iteration i: the row iteration i + la loads into the ring
-      for (int32_t i = 0; i + la < iters; i++) ent[i * E] = ent[(i + la) * E + 1];
-    }
-    return true;
-  }
-
-  std::mutex mu_;
-  std::map<std::tuple<int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t>,
-           std::unique_ptr<DevSched>>
-      map_;
-};
-
-SchedCache& schedules() {
-  static SchedCache* c = new SchedCache();
-  return *c;
+  return true;
 }
 
 mxd::AxisView axis_view(const DevTable& t) {
   return mxd::AxisView{t.first.data(), t.count.data(), t.w.data(), t.width, t.padded};
 }
 
-// Band-kernel schedules (layout: band_plan.h) in device memory, one per
-// (device, vertical geometry, crop rows, band height, class, least groups per band).
-class BandSchedCache {
+// Key: the schedule's kind, the device, then what its words depend on.
+// build(words, sched) writes the words and their band_words / entry_off.
+class SchedCache {
  public:
-  int get(int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h, int32_t crop_y, int32_t crop_h,
-          int32_t ty, int32_t db, int32_t s, int32_t min_groups, const DevSched** out) {
+  using Key = std::tuple<int32_t, int32_t, std::array<int32_t, 9>>;
+  explicit SchedCache(bool upload) : upload_(upload) {}
+  template <class Build>
+  int get(const Key& key, const char* misfit, Build build, const DevSched** out) {
     std::lock_guard<std::mutex> lock(mu_);
-    const auto key = std::make_tuple(device, src_h, resize_h, crop_y, crop_h, ty, db, s, min_groups);
     auto it = map_.find(key);
     if (it != map_.end()) {
       *out = it->second.get();
@@ -160,26 +126,49 @@ class BandSchedCache {
     }
     auto sched = std::make_unique<DevSched>();
     std::vector<int32_t> words;
-    if (!mxd::band_schedule(axis_view(yt), crop_y, crop_h, ty, db, s, min_groups, &words, &sched->band_words))
-      return fail(MXD_ERR_INVALID, "mxd: band schedule does not fit its class");
-    DeviceGuard g(device);
-    MXD_HIP(hipMalloc(reinterpret_cast<void**>(&sched->ptr), words.size() * sizeof(int32_t)));
-    MXD_HIP(hipMemcpy(sched->ptr, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!build(&words, sched.get())) return fail(MXD_ERR_INVALID, misfit);
+    if (upload_) {
+      DeviceGuard g(std::get<1>(key));
+      MXD_HIP(hipMalloc(reinterpret_cast<void**>(&sched->ptr), words.size() * sizeof(int32_t)));
+      MXD_HIP(hipMemcpy(sched->ptr, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
     *out = sched.get();
     map_[key] = std::move(sched);
     return MXD_OK;
   }
 
  private:
+  bool upload_;
   std::mutex mu_;
-  std::map<std::tuple<int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t>,
-           std::unique_ptr<DevSched>>
-      map_;
+  std::map<Key, std::unique_ptr<DevSched>> map_;
 };
 
-BandSchedCache& band_schedules() {
-  static BandSchedCache* c = new BandSchedCache();
+SchedCache& schedules() {
+  static SchedCache* c = new SchedCache(true);  // leaked on purpose, like tables()
   return *c;
+}
+
+SchedCache& host_schedules() {
+  static SchedCache* c = new SchedCache(false);
+  return *c;
+}
+
+int scatter_schedule(SchedCache& cache, int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h,
+                     int32_t crop_y, int32_t crop_h, int32_t ty, const ScatterShape& sh, const DevSched** out) {
+  const SchedCache::Key key{0, device, {src_h, resize_h, crop_y, crop_h, ty, sh.s, sh.dmax, sh.p, sh.lane_bytes}};
+  return cache.get(key, "mxd: scatter schedule does not fit its shape", [&](std::vector<int32_t>* words, DevSched* d) {
+    return scatter_schedule_words(yt, crop_y, crop_h, ty, sh, words, &d->band_words, &d->entry_off);
+  }, out);
+}
+
+// The band kernel's (layout: band_plan.h): per class and least groups per band.
+int band_schedule_dev(SchedCache& cache, int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h,
+                      int32_t crop_y, int32_t crop_h, int32_t ty, int32_t db, int32_t s, int32_t min_groups,
+                      const DevSched** out) {
+  const SchedCache::Key key{1, device, {src_h, resize_h, crop_y, crop_h, ty, db, s, min_groups, 0}};
+  return cache.get(key, "mxd: band schedule does not fit its class", [&](std::vector<int32_t>* words, DevSched* d) {
+    return mxd::band_schedule(axis_view(yt), crop_y, crop_h, ty, db, s, min_groups, words, &d->band_words);
+  }, out);
 }
 
 // Wave path strips: q output pixels per lane (strip_cols <= 64 q) and every
@@ -331,8 +320,9 @@ bool wave_strips_bytes(const DevTable& xt, const mxd_image& im, const Stored& st
 // policy bit turns it off, so those policies keep selecting what they name.
 constexpr int32_t kWavePolicies = MXD_POLICY_NO_SCATTER | MXD_POLICY_NO_WAVE | MXD_POLICY_NARROW |
                                   MXD_POLICY_NO_BYTES | MXD_POLICY_BYTES;
-void plan_band(const mxd_image& im, const Stored& st, int32_t f32, ImgPlan& p) {
+void plan_band(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan& p) {
   p.band = false;
+  const int32_t f32 = out_dtype == MXD_F32_DIV255 ? 1 : 0;
   if (g_policy.load() & (MXD_POLICY_NO_BAND | kWavePolicies)) return;
   const int64_t c = im.channels, elem = f32 ? 4 : 1;
   const int64_t shift = (int64_t)(reinterpret_cast<uintptr_t>(st.base) & 3);
@@ -383,8 +373,9 @@ bool scatter_kernel_for(int32_t c, int32_t f32, int32_t xw, const ScatterShape& 
 // over the lane widths available for its channel count, the one that cuts
 // the crop into the fewest strips (narrow strips read more halo and more,
 // shorter row pieces), then the narrower lane width.
-void plan_wave(const mxd_image& im, const Stored& st, int32_t f32, int32_t out_dtype, ImgPlan& p) {
+void plan_wave(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan& p) {
   p.wave = false;
+  const int32_t f32 = out_dtype == MXD_F32_DIV255 ? 1 : 0;
   p.ycc = false;
   const bool ycc = st.ycc != nullptr;
   if (ycc) {
@@ -482,20 +473,10 @@ bool ycc_plan_ok(const mxd_image& im, const Stored& st, int32_t out_dtype, int32
   ImgPlan p;
   if (tables().get(device, im.src_w, im.resize_w, &p.xt) != MXD_OK) return false;
   if (tables().get(device, im.src_h, im.resize_h, &p.yt) != MXD_OK) return false;
-  plan_wave(im, st, out_dtype == MXD_F32_DIV255 ? 1 : 0, out_dtype, p);
+  plan_wave(im, st, out_dtype, p);
   return p.wave && p.ycc;
 }
 
-
-int scatter_schedule(int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h, int32_t crop_y,
-                     int32_t crop_h, int32_t ty, const ScatterShape& sh, const DevSched** out) {
-  return schedules().get(device, yt, src_h, resize_h, crop_y, crop_h, ty, sh, out);
-}
-
-int band_schedule_dev(int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h, int32_t crop_y, int32_t crop_h,
-                  int32_t ty, int32_t db, int32_t s, int32_t min_groups, const DevSched** out) {
-  return band_schedules().get(device, yt, src_h, resize_h, crop_y, crop_h, ty, db, s, min_groups, out);
-}
 
 }  // namespace capi
 }  // namespace mxd

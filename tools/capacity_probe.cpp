@@ -33,7 +33,7 @@ int main() {
     ImgPlan p;
     tables().get(0, m.src_w, m.resize_w, &p.xt);
     tables().get(0, m.src_h, m.resize_h, &p.yt);
-    plan_wave(m, whole(m), w.f32 ? 1 : 0, w.f32 ? MXD_F32_DIV255 : MXD_U8, p);
+    plan_wave(m, whole(m), w.f32 ? MXD_F32_DIV255 : MXD_U8, p);
     const mxd::WaveCfg cfg{3, w.f32 ? 1 : 0, p.bucket, 0, 0, p.kind, p.s, p.dmax, p.q, p.shift, p.pp};
     int blocks = -1, vgprs = -1, lds = -1;
     const int wpb = mxd::wave_kernel_info(cfg, 0, &blocks, &vgprs, &lds);
