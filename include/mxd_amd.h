@@ -49,8 +49,14 @@ extern "C" {
  * 7, added without a new number (test for the symbols): formatted outputs --
  * mxd_elem, mxd_layout, mxd_out_format, mxd_out_format_table,
  * mxd_resize_crop_batch_fmt, mxd_resize_crop_to_device_fmt,
- * mxd_jpeg_resize_crop_to_device_fmt. */
+ * mxd_jpeg_resize_crop_to_device_fmt.
+ * 7, added without a new number (test for MXD_HAS_FILTERS / the symbol):
+ * resampling filters -- mxd_filter, mxd_image::filter and
+ * mxd_jpeg_image::filter (the former `reserved` fields: same layout, 0 =
+ * triangle keeps every zero-initialising caller as it was), and
+ * mxd_axis_taps_filter. */
 #define MXD_ABI_VERSION 7
+#define MXD_HAS_FILTERS 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -65,6 +71,26 @@ enum mxd_dtype {
   MXD_U8 = 0,          /* uint8, as core::image::resize + crop produce */
   MXD_F32_DIV255 = 1   /* float32 q/255.0f of the uint8 result, bit-exact to the
                           NumPy x.astype("float32")/255 the reference benchmark runs */
+};
+
+/* Resampling filter of one image's resize (both axes).  MXD_FILTER_TRIANGLE is
+ * what core::image::resize forces on stbir; the cubics are stbir's kernels of
+ * support 2 (x = |distance|):
+ *   Catmull-Rom (PIL BICUBIC, torch bicubic, a = -0.5):
+ *     x<1: 1 - x^2 (2.5 - 1.5x)          x<2: 2 - x(4 + x(0.5x - 2.5))
+ *   Mitchell:
+ *     x<1: (16 + x^2 (21x - 36))/18      x<2: (32 + x(-60 + x(36 - 7x)))/18
+ *   B-spline:
+ *     x<1: (4 + x^2 (3x - 6))/6          x<2: (8 + x(-12 + x(6 - x)))/6
+ * Downsampling widens the kernel by 1/scale (antialiasing); edges clamp; each
+ * output's weights are renormalised to sum 1; negative lobes may overshoot and
+ * the u8 encode clamps them.  An axis with out == in is the identity for every
+ * filter.  Any other value: MXD_ERR_INVALID. */
+enum mxd_filter {
+  MXD_FILTER_TRIANGLE = 0,
+  MXD_FILTER_CATMULLROM = 1,
+  MXD_FILTER_MITCHELL = 2,
+  MXD_FILTER_CUBICBSPLINE = 3
 };
 
 /*
@@ -88,6 +114,7 @@ enum mxd_dtype {
  *                zero = channels filtered independently, which an identity
  *                resize turns into the exact copy a pure crop / flip is
  *                (array::sub / hflip never call stbir)
+ *   filter       mxd_filter of the resize (0 = triangle, the reference's)
  */
 typedef struct mxd_image {
   const uint8_t* src;
@@ -99,7 +126,7 @@ typedef struct mxd_image {
   void* dst;
   int64_t dst_stride;
   int32_t rgba_weighted;
-  int32_t reserved;
+  int32_t filter;
 } mxd_image;
 
 /* ---- library / errors ------------------------------------------------- */
@@ -127,6 +154,9 @@ int mxd_center_crop_origin(int64_t w, int64_t h, int64_t cw, int64_t ch, int64_t
  * MXD_ERR_INVALID is returned. */
 int mxd_axis_taps(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t crop_len, int32_t max_taps,
                   int32_t* first, int32_t* ntaps, float* weights, int32_t* taps_needed);
+/* The same for any mxd_filter (mxd_axis_taps is its filter-0 form). */
+int mxd_axis_taps_filter(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t crop_len, int32_t filter,
+                         int32_t max_taps, int32_t* first, int32_t* ntaps, float* weights, int32_t* taps_needed);
 
 /* ---- the hot path -------------------------------------------------------- */
 
@@ -397,7 +427,7 @@ typedef struct mxd_jpeg_image {
   int32_t resize_w, resize_h;
   int32_t crop_x, crop_y, crop_w, crop_h;
   int32_t flip;
-  int32_t reserved;
+  int32_t filter; /* mxd_filter, as mxd_image::filter */
   void* dst;
   int64_t dst_stride;
 } mxd_jpeg_image;

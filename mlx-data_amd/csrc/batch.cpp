@@ -167,6 +167,7 @@ int validate(const mxd_image& im, int32_t i) {
   if (im.crop_x + im.crop_w > im.resize_w || im.crop_y + im.crop_h > im.resize_h)
     return at("Array: sub: shape out of bound");
   if (im.src_stride < (int64_t)im.src_w * im.channels) return at("mxd: src_stride smaller than a row");
+  if (im.filter < 0 || im.filter >= mxd::kFilterCount) return at("mxd: unknown filter");
   return MXD_OK;
 }
 

@@ -49,8 +49,8 @@ int plan_images(Batch& b) {
       p = b.L.plans[b.rep[i]];
       continue;
     }
-    if (int rc = b.env.tables->get(b.device, im.src_w, im.resize_w, &p.xt)) return rc;
-    if (int rc = b.env.tables->get(b.device, im.src_h, im.resize_h, &p.yt)) return rc;
+    if (int rc = b.env.tables->get(b.device, im.src_w, im.resize_w, &p.xt, im.filter)) return rc;
+    if (int rc = b.env.tables->get(b.device, im.src_h, im.resize_h, &p.yt, im.filter)) return rc;
     if (st.ycc) {
       // JPEG planes (the host path checked ycc_plan_ok): a wave kernel or nothing
       plan_wave(im, st, b.out_dtype, p);
@@ -62,6 +62,15 @@ int plan_images(Batch& b) {
       } else {
         plan_wave(im, st, b.out_dtype, p);
         if (!p.wave) plan_band(im, st, b.out_dtype, p);
+      }
+      // A formatted call keeps a wave kernel only where its formatted form
+      // exists (every shape of wave.hip; not the cubic filters' shapes): the
+      // others are resized into u8 scratch rows by the band or general kernel.
+      if (b.formatted && p.wave &&
+          !mxd::wave_has_kernel(mxd::WaveCfg{b.channels, mxd::kWaveOutFmt, p.bucket, 0, 0, p.kind, p.s, p.dmax, p.q,
+                                             p.shift, p.pp})) {
+        p.wave = false;
+        plan_band(im, st, b.out_dtype, p);
       }
     }
   }
@@ -220,6 +229,7 @@ int wave_groups(Batch& b) {
   for (BatchLayout::WaveGroup& g : b.L.waves) {
     g.cfg.nimgs = g.count;
     g.cfg.nt = g.cfg.ycc ? 0 : nt;
+    if (g.cfg.nt && !mxd::wave_has_kernel(g.cfg)) g.cfg.nt = 0;  // shapes built with the default policy only
     const int32_t capacity = b.env.wave_capacity >= 0 ? b.env.wave_capacity : wave_capacity_cached(g.cfg, b.device);
     g.ty = band_rows(group_strips(b, g, false), capacity);
     auto sched = [&](int32_t i, int32_t rows, const DevSched** out) {

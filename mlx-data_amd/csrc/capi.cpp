@@ -217,8 +217,16 @@ int mxd_center_crop_origin(int64_t w, int64_t h, int64_t cw, int64_t ch, int64_t
 
 int mxd_axis_taps(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t crop_len, int32_t max_taps,
                   int32_t* first, int32_t* ntaps, float* weights, int32_t* taps_needed) {
+  return mxd_axis_taps_filter(in_size, out_size, crop_off, crop_len, MXD_FILTER_TRIANGLE, max_taps, first, ntaps,
+                              weights, taps_needed);
+}
+
+int mxd_axis_taps_filter(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t crop_len, int32_t filter,
+                         int32_t max_taps, int32_t* first, int32_t* ntaps, float* weights, int32_t* taps_needed) {
+  if (filter < 0 || filter >= mxd::kFilterCount)
+    return fail(MXD_ERR_INVALID, "mxd: unknown filter " + std::to_string(filter));
   mxd::AxisTaps t;
-  if (!mxd::build_axis_taps(in_size, out_size, crop_off, crop_len, &t))
+  if (!mxd::build_axis_taps(in_size, out_size, crop_off, crop_len, &t, filter))
     return fail(MXD_ERR_INVALID, "mxd: invalid axis geometry");
   if (taps_needed) *taps_needed = t.width;
   if (t.width > max_taps) return fail(MXD_ERR_INVALID, "mxd: max_taps too small");
@@ -253,8 +261,8 @@ int mxd_describe_band_plan(const mxd_image* image, int32_t out_dtype, int32_t* i
   if (!image || !info12) return fail(MXD_ERR_INVALID, "mxd: null argument");
   if (int rc = validate(*image, 0)) return rc;
   ImgPlan p;
-  if (int rc = host_tables().get(0, image->src_w, image->resize_w, &p.xt)) return rc;
-  if (int rc = host_tables().get(0, image->src_h, image->resize_h, &p.yt)) return rc;
+  if (int rc = host_tables().get(0, image->src_w, image->resize_w, &p.xt, image->filter)) return rc;
+  if (int rc = host_tables().get(0, image->src_h, image->resize_h, &p.yt, image->filter)) return rc;
   plan_band(*image, whole(*image), out_dtype, p);
   const mxd::BandPlan& b = p.bp;
   mxd::BandCfg cfg{};
@@ -271,8 +279,8 @@ int mxd_describe_plan(const mxd_image* image, int32_t out_dtype, int32_t device,
   if (!image || !info8) return fail(MXD_ERR_INVALID, "mxd: null argument");
   if (int rc = validate(*image, 0)) return rc;
   ImgPlan p;
-  if (int rc = host_tables().get(device, image->src_w, image->resize_w, &p.xt)) return rc;
-  if (int rc = host_tables().get(device, image->src_h, image->resize_h, &p.yt)) return rc;
+  if (int rc = host_tables().get(device, image->src_w, image->resize_w, &p.xt, image->filter)) return rc;
+  if (int rc = host_tables().get(device, image->src_h, image->resize_h, &p.yt, image->filter)) return rc;
   if (!(g_policy.load() & MXD_POLICY_NO_WAVE)) plan_wave(*image, whole(*image), out_dtype, p);
   const int32_t v[8] = {p.wave ? 1 : 0, p.kind, p.bucket, p.s, p.dmax, p.q, p.nstrips, p.pp};
   std::memcpy(info8, v, sizeof v);

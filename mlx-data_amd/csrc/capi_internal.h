@@ -77,12 +77,13 @@ extern std::atomic<int32_t> g_policy;
 extern std::atomic<int32_t> g_tune[MXD_TUNE_COUNT];
 
 // ---------------------------------------------------------------------------
-// Device tap tables: one per (device, in_size, out_size), covering every
+// Device tap tables: one per (device, in_size, out_size, filter), covering every
 // output pixel of the axis, so any crop window is a pointer offset into it.
 struct DevTable {
   float* ptr = nullptr;
   int32_t width = 0;     // max taps of any output
   int32_t padded = 0;    // weights per entry in device memory (>= kMinTabWidth)
+  int32_t filter = 0;    // mxd_filter the weights were built with (0 for an identity axis)
   std::vector<int32_t> first, count;  // host copy for tiling decisions
   std::vector<float> w;               // host copy of the weights, `width` per output (scatter schedules)
 };
@@ -91,16 +92,19 @@ class TableCache {
  public:
   // upload = false: host copies only (ptr stays null), for planning without a device.
   explicit TableCache(bool upload = true) : upload_(upload) {}
-  int get(int32_t device, int32_t in, int32_t out, const DevTable** out_tab) {
+  int get(int32_t device, int32_t in, int32_t out, const DevTable** out_tab, int32_t filter = 0) {
+    if (filter < 0 || filter >= mxd::kFilterCount)
+      return fail(MXD_ERR_INVALID, "mxd: unknown filter " + std::to_string(filter));
+    if (in == out) filter = 0;  // the identity for every filter: one table
     std::lock_guard<std::mutex> lock(mu_);
-    auto key = std::make_tuple(device, in, out);
+    auto key = std::make_tuple(device, in, out, filter);
     auto it = map_.find(key);
     if (it != map_.end()) {
       *out_tab = it->second.get();
       return MXD_OK;
     }
     mxd::AxisTaps taps;
-    if (!mxd::build_axis_taps(in, out, 0, out, &taps))
+    if (!mxd::build_axis_taps(in, out, 0, out, &taps, filter))
       return fail(MXD_ERR_INVALID, "image: cannot create image with 0 or negative dimension");
     const int32_t padded = std::max<int32_t>(taps.width, mxd::kMinTabWidth);
     const int32_t stride = mxd::kTapHeader + padded;
@@ -114,6 +118,7 @@ class TableCache {
     auto tab = std::make_unique<DevTable>();
     tab->width = taps.width;
     tab->padded = padded;
+    tab->filter = filter;
     tab->first = taps.first;
     tab->count = taps.count;
     tab->w = taps.weight;
@@ -130,7 +135,7 @@ class TableCache {
  private:
   bool upload_;
   std::mutex mu_;
-  std::map<std::tuple<int32_t, int32_t, int32_t>, std::unique_ptr<DevTable>> map_;
+  std::map<std::tuple<int32_t, int32_t, int32_t, int32_t>, std::unique_ptr<DevTable>> map_;
 };
 
 TableCache& tables();
@@ -230,7 +235,7 @@ bool ycc_plan_ok(const mxd_image& im, const Stored& st, int32_t out_dtype, int32
 // What a plan depends on: geometry, the stored region's layout and the
 // alignments of source and destination.
 struct PlanKey {
-  int32_t v[20];
+  int32_t v[21];
   bool operator==(const PlanKey& o) const { return std::memcmp(v, o.v, sizeof v) == 0; }
 };
 struct PlanKeyHash {

@@ -302,8 +302,8 @@ int jpeg_plan_input(HostCall& c, int32_t i) {
   // window when the geometry has no tables: run_batch reports that)
   const DevTable *xt = nullptr, *yt = nullptr;
   int32_t xl = 0, xh = im.src_w - 1, yl = 0, yh = im.src_h - 1;
-  if (tables().get(c.device, im.src_w, im.resize_w, &xt) == MXD_OK &&
-      tables().get(c.device, im.src_h, im.resize_h, &yt) == MXD_OK)
+  if (tables().get(c.device, im.src_w, im.resize_w, &xt, im.filter) == MXD_OK &&
+      tables().get(c.device, im.src_h, im.resize_h, &yt, im.filter) == MXD_OK)
     footprint(*xt, *yt, im, &xl, &xh, &yl, &yh);
   s.foot = {ji.win_x + xl, ji.win_x + xh, ji.win_y + yl, ji.win_y + yh};
   return MXD_OK;
@@ -444,6 +444,7 @@ int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t 
     m.crop_w = j.crop_w;
     m.crop_h = j.crop_h;
     m.flip = j.flip;
+    m.filter = j.filter;
     m.dst = j.dst;
     m.dst_stride = j.dst_stride;
   }

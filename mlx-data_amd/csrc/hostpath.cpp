@@ -389,8 +389,8 @@ struct Drain {
 int raw_plan_input(HostCall& c, int32_t i) {
   const mxd_image& im = c.images[i];
   const DevTable *xt = nullptr, *yt = nullptr;
-  if (int rc = tables().get(c.device, im.src_w, im.resize_w, &xt)) return rc;
-  if (int rc = tables().get(c.device, im.src_h, im.resize_h, &yt)) return rc;
+  if (int rc = tables().get(c.device, im.src_w, im.resize_w, &xt, im.filter)) return rc;
+  if (int rc = tables().get(c.device, im.src_h, im.resize_h, &yt, im.filter)) return rc;
   int32_t xl, xh, yl, yh;
   footprint(*xt, *yt, im, &xl, &xh, &yl, &yh);
   const int32_t ch = im.channels;

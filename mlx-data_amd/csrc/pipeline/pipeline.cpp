@@ -181,6 +181,7 @@ mxd_image plan_desc(const ImagePlan& p, void* dst, int64_t dst_stride) {
   d.crop_h = (int32_t)p.crop_h;
   d.flip = p.flip ? 1 : 0;
   d.rgba_weighted = p.resampled && c == 4 ? 1 : 0;
+  d.filter = p.filter;
   d.dst = dst;
   d.dst_stride = dst_stride;
   return d;
@@ -207,6 +208,7 @@ mxd_jpeg_image jpeg_desc(const ImagePlan& p, const JpegSource& j, void* dst, int
   d.crop_w = (int32_t)p.crop_w;
   d.crop_h = (int32_t)p.crop_h;
   d.flip = p.flip ? 1 : 0;
+  d.filter = p.filter;
   d.dst = dst;
   d.dst_stride = dst_stride;
   return d;
@@ -619,7 +621,7 @@ void verify_dimensions(int64_t w, int64_t h, int64_t c) {
 std::shared_ptr<Array> make(const ImagePlan& p) { return std::make_shared<Array>(std::make_shared<const ImagePlan>(p)); }
 
 // core::image::resize (core/image/ImageTransform.cpp:41-62).
-std::shared_ptr<Array> plan_resize(const std::shared_ptr<Array>& img, int64_t dw, int64_t dh) {
+std::shared_ptr<Array> plan_resize(const std::shared_ptr<Array>& img, int64_t dw, int64_t dh, int filter) {
   verify_dimensions(dw, dh, img->shape(2));
   ImagePlan p = view(img);
   // (an alpha-weighted same-size resize is not the identity: it zeroes the
@@ -643,6 +645,7 @@ std::shared_ptr<Array> plan_resize(const std::shared_ptr<Array>& img, int64_t dw
   p.crop_x = p.crop_y = 0;
   p.flip = false;
   p.resampled = true;
+  p.filter = filter;
   return make(p);
 }
 
@@ -672,6 +675,19 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
 }
 
 }  // namespace
+
+namespace {
+const char* const kFilterNames[] = {"triangle", "catmullrom", "mitchell", "cubicbspline"};
+}
+
+int parse_filter(const std::string& name) {
+  for (int f = 0; f < 4; f++)
+    if (name == kFilterNames[f]) return f;
+  throw std::invalid_argument("image_resize: unknown filter '" + name +
+                              "' (one of triangle, catmullrom, mitchell, cubicbspline)");
+}
+
+const char* filter_name(int filter) { return kFilterNames[filter >= 0 && filter < 4 ? filter : 0]; }
 
 // op/ImageTransform.cpp:22-31 + core/image/ImageIO.cpp:39-49 + core/video/Video.cpp:69-79
 std::shared_ptr<Array> ImageOp::apply_key(const std::shared_ptr<Array>& x) const {
@@ -730,12 +746,12 @@ std::shared_ptr<Array> ImageResizeSmallestSide::apply_image(const std::shared_pt
   if (size_ <= 0) throw std::runtime_error("ImageResizeSmallestSide: illegal target size: " + std::to_string(size_));
   const int64_t w = img->shape(1), h = img->shape(0);
   const double scale = h > w ? (double)size_ / w : (double)size_ / h;
-  return plan_resize(img, std::lround(scale * w), std::lround(scale * h));
+  return plan_resize(img, std::lround(scale * w), std::lround(scale * h), filter_);
 }
 
 // op/ImageTransform.cpp:103-106
 std::shared_ptr<Array> ImageResize::apply_image(const std::shared_ptr<Array>& img) const {
-  return plan_resize(img, w_, h_);
+  return plan_resize(img, w_, h_, filter_);
 }
 
 // op/ImageTransform.cpp:115-126

@@ -80,6 +80,9 @@ struct ImagePlan {
   // Went through core::image::resize (stbir): 4-channel images are then
   // alpha-weighted (STBIR_RGBA); crops and mirrors alone never are.
   bool resampled = false;
+  // mxd_filter of the pending resize (0 = triangle, the reference's).  One
+  // plan holds one resize: a second one materialises the first.
+  int filter = 0;
   // image_to_float: the kernel writes float32 q / 255 (MXD_F32_DIV255)
   // instead of the uint8 q; the array's type is then Float.
   bool f32 = false;
@@ -214,24 +217,33 @@ std::shared_ptr<Array> video_frame(const std::shared_ptr<Array>& video, int64_t 
 // Stacks per-frame results (pending plans in one launch) into (F, h, w, c).
 std::shared_ptr<Array> stack_frames(const std::vector<std::shared_ptr<Array>>& frames);
 
+// The resize ops' `filter` argument: "triangle" (the reference's, the
+// default), "catmullrom" (PIL BICUBIC / torch bicubic), "mitchell",
+// "cubicbspline" -> mxd_filter.  Any other name: std::invalid_argument
+// (Python: ValueError) naming the four.
+int parse_filter(const std::string& name);
+const char* filter_name(int filter);
+
 class ImageResizeSmallestSide : public ImageOp {
  public:
-  ImageResizeSmallestSide(std::string ikey, int64_t size, std::string okey)
-      : ImageOp(std::move(ikey), std::move(okey)), size_(size) {}
+  ImageResizeSmallestSide(std::string ikey, int64_t size, std::string okey, int filter = 0)
+      : ImageOp(std::move(ikey), std::move(okey)), size_(size), filter_(filter) {}
   std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
 
  private:
   int64_t size_;
+  int filter_;
 };
 
 class ImageResize : public ImageOp {
  public:
-  ImageResize(std::string ikey, int64_t w, int64_t h, std::string okey)
-      : ImageOp(std::move(ikey), std::move(okey)), w_(w), h_(h) {}
+  ImageResize(std::string ikey, int64_t w, int64_t h, std::string okey, int filter = 0)
+      : ImageOp(std::move(ikey), std::move(okey)), w_(w), h_(h), filter_(filter) {}
   std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
 
  private:
   int64_t w_, h_;
+  int filter_;
 };
 
 class ImageCenterCrop : public ImageOp {

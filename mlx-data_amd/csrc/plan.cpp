@@ -114,7 +114,7 @@ mxd::AxisView axis_view(const DevTable& t) {
 // build(words, sched) writes the words and their band_words / entry_off.
 class SchedCache {
  public:
-  using Key = std::tuple<int32_t, int32_t, std::array<int32_t, 9>>;
+  using Key = std::tuple<int32_t, int32_t, std::array<int32_t, 10>>;
   explicit SchedCache(bool upload) : upload_(upload) {}
   template <class Build>
   int get(const Key& key, const char* misfit, Build build, const DevSched** out) {
@@ -155,7 +155,7 @@ SchedCache& host_schedules() {
 
 int scatter_schedule(SchedCache& cache, int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h,
                      int32_t crop_y, int32_t crop_h, int32_t ty, const ScatterShape& sh, const DevSched** out) {
-  const SchedCache::Key key{0, device, {src_h, resize_h, crop_y, crop_h, ty, sh.s, sh.dmax, sh.p, sh.lane_bytes}};
+  const SchedCache::Key key{0, device, {src_h, resize_h, crop_y, crop_h, ty, sh.s, sh.dmax, sh.p, sh.lane_bytes, yt.filter}};
   return cache.get(key, "mxd: scatter schedule does not fit its shape", [&](std::vector<int32_t>* words, DevSched* d) {
     return scatter_schedule_words(yt, crop_y, crop_h, ty, sh, words, &d->band_words, &d->entry_off);
   }, out);
@@ -165,7 +165,7 @@ int scatter_schedule(SchedCache& cache, int32_t device, const DevTable& yt, int3
 int band_schedule_dev(SchedCache& cache, int32_t device, const DevTable& yt, int32_t src_h, int32_t resize_h,
                       int32_t crop_y, int32_t crop_h, int32_t ty, int32_t db, int32_t s, int32_t min_groups,
                       const DevSched** out) {
-  const SchedCache::Key key{1, device, {src_h, resize_h, crop_y, crop_h, ty, db, s, min_groups, 0}};
+  const SchedCache::Key key{1, device, {src_h, resize_h, crop_y, crop_h, ty, db, s, min_groups, 0, yt.filter}};
   return cache.get(key, "mxd: band schedule does not fit its class", [&](std::vector<int32_t>* words, DevSched* d) {
     return mxd::band_schedule(axis_view(yt), crop_y, crop_h, ty, db, s, min_groups, words, &d->band_words);
   }, out);
@@ -379,6 +379,9 @@ void plan_wave(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan
   p.ycc = false;
   const bool ycc = st.ycc != nullptr;
   if (ycc) {
+    // the cubic filters' kernels read RGB frames only (wave_cubic.hip): their
+    // JPEG images take the RGB-frame route
+    if (p.xt->filter != 0 || p.yt->filter != 0) return;
     // JPEG planes: the RGB-row layout rules do not apply, only the output's
     const uintptr_t o = reinterpret_cast<uintptr_t>(im.dst) | (uintptr_t)im.dst_stride;
     if (im.channels != 3 || ((reinterpret_cast<uintptr_t>(st.base) | (uintptr_t)st.stride) & 3) != 0 ||
@@ -391,8 +394,12 @@ void plan_wave(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan
   const int32_t shift = (reinterpret_cast<uintptr_t>(st.base) & 3) != 0 ? 1 : 0;
   // Scatter when the vertical axis downsamples into a shape with a kernel,
   // else gather.
-  const ScatterShape sh =
+  ScatterShape sh =
       (g_policy.load() & MXD_POLICY_NO_SCATTER) ? ScatterShape{} : scatter_shape(*p.yt, im.crop_y, im.crop_h);
+  // The S = 4 kernels are the cubic filters' (wave_cubic.hip).  A triangle
+  // table can have that shape too (a downscale close to 1 : 1): it keeps the
+  // route it had before those kernels existed, the gather kernel.
+  if (sh.s >= 4 && p.yt->filter == 0) sh = ScatterShape{};
   const int32_t gb = mxd::wave_taps_bucket(std::max(p.xt->width, p.yt->width));
   const int32_t dp = mxd::wave_default_p(c);
   const int32_t policy = g_policy.load();
@@ -465,14 +472,14 @@ PlanKey plan_key(const mxd_image& im, const Stored& st) {
   return PlanKey{{im.src_w, im.src_h, im.channels, im.resize_w, im.resize_h, im.crop_x, im.crop_y, im.crop_w,
                   im.crop_h, im.flip ? 1 : 0, im.rgba_weighted, st.x0, st.rows, (int32_t)ss, (int32_t)(ss >> 32),
                   (int32_t)ds, (int32_t)(ds >> 32), (int32_t)(reinterpret_cast<uintptr_t>(st.base) & 15),
-                  (int32_t)(reinterpret_cast<uintptr_t>(im.dst) & 15), st.ycc ? 1 : 0}};
+                  (int32_t)(reinterpret_cast<uintptr_t>(im.dst) & 15), st.ycc ? 1 : 0, im.filter}};
 }
 
 bool ycc_plan_ok(const mxd_image& im, const Stored& st, int32_t out_dtype, int32_t device) {
   if (!st.ycc || (g_policy.load() & MXD_POLICY_NO_WAVE)) return false;
   ImgPlan p;
-  if (tables().get(device, im.src_w, im.resize_w, &p.xt) != MXD_OK) return false;
-  if (tables().get(device, im.src_h, im.resize_h, &p.yt) != MXD_OK) return false;
+  if (tables().get(device, im.src_w, im.resize_w, &p.xt, im.filter) != MXD_OK) return false;
+  if (tables().get(device, im.src_h, im.resize_h, &p.yt, im.filter) != MXD_OK) return false;
   plan_wave(im, st, out_dtype, p);
   return p.wave && p.ycc;
 }

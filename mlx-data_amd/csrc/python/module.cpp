@@ -326,16 +326,19 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
           py::arg("from_memory") = false, py::arg("output_key") = "")
       .def(
           "image_resize_smallest_side",
-          [wrap](const Self& self, const std::string& key, int64_t size, const std::string& output_key) {
-            return wrap(self, std::make_shared<ImageResizeSmallestSide>(key, size, output_key));
+          [wrap](const Self& self, const std::string& key, int64_t size, const std::string& output_key,
+                 const std::string& filter) {
+            return wrap(self, std::make_shared<ImageResizeSmallestSide>(key, size, output_key, parse_filter(filter)));
           },
-          py::arg("key"), py::arg("size"), py::arg("output_key") = "")
+          py::arg("key"), py::arg("size"), py::arg("output_key") = "", py::kw_only(), py::arg("filter") = "triangle")
       .def(
           "image_resize",
-          [wrap](const Self& self, const std::string& key, int64_t w, int64_t h, const std::string& output_key) {
-            return wrap(self, std::make_shared<ImageResize>(key, w, h, output_key));
+          [wrap](const Self& self, const std::string& key, int64_t w, int64_t h, const std::string& output_key,
+                 const std::string& filter) {
+            return wrap(self, std::make_shared<ImageResize>(key, w, h, output_key, parse_filter(filter)));
           },
-          py::arg("key"), py::arg("w"), py::arg("h"), py::arg("output_key") = "")
+          py::arg("key"), py::arg("w"), py::arg("h"), py::arg("output_key") = "", py::kw_only(),
+          py::arg("filter") = "triangle")
       .def(
           "image_center_crop",
           [wrap](const Self& self, const std::string& key, int64_t w, int64_t h, const std::string& output_key) {
@@ -609,6 +612,7 @@ PYBIND11_MODULE(_pipeline, m) {
     d["resize"] = py::make_tuple(p.resize_w, p.resize_h);
     d["crop"] = py::make_tuple(p.crop_x, p.crop_y, p.crop_w, p.crop_h);
     d["flip"] = p.flip;
+    d["filter"] = filter_name(p.filter);
     d["shape"] = a->shape();
     if (p.formatted) {
       static const char* const elems[] = {"float32", "float16", "bfloat16"};

@@ -156,12 +156,20 @@ int wave_byte_window();
 int wave_plane_floats(int channels, int p);  // LDS floats per wave
 int wave_lanes();
 int launch_wave(const WaveCfg& cfg, const ImgDev* imgs, void* stream);
+// Whether cfg's kernel exists, in its output mode (formatted: wave_fmt.hip)
+// and with its load policy (cfg.nt).
 bool wave_has_kernel(const WaveCfg& cfg);
+// The scatter shapes of the cubic filters (wave_cubic.hip: S = 4, RGB, u8 and
+// f32 modes, default load policy): the kernel of cfg (a WaveKernel), or null.
+// wave_has_kernel / launch_wave / wave_capacity look there after wave.hip's own.
+void* wave_cubic_kernel(const WaveCfg& cfg);
 // The formatted-output kernels (wave_fmt.hip; cfg.f32 == kWaveOutFmt): every
-// shape wave.hip has in the other two modes, so wave_has_kernel() of the u8
-// form answers for them too; wave_capacity() forwards to wave_fmt_capacity().
+// shape wave.hip itself has in the other two modes (not wave_cubic.hip's: a
+// formatted call resizes those images into u8 scratch rows and formats them
+// with format_rows); wave_capacity() forwards to wave_fmt_capacity().
 int launch_wave_fmt(const WaveCfg& cfg, const ImgDev* imgs, const OutFmtDev& fmt, void* stream);
 int wave_fmt_capacity(const WaveCfg& cfg, int device);
+bool wave_fmt_has_kernel(const WaveCfg& cfg);
 // u8 rows -> formatted rows (format_rows.hip): the second pass of the images
 // the band and general kernels resize.  rows: device array of nimgs entries;
 // one workgroup per kFmtRows rows of an image (nblocks in all, numbered

@@ -14,6 +14,14 @@
 //   num/den with num < out the first `num` outputs are built and repeated
 //   with the input shifted by `den` (polyphase); out-of-range taps are folded
 //   onto pixel 0 / in-1 (clamp) and zero taps trimmed.
+// The cubic filters (Catmull-Rom, Mitchell, B-spline: stbir's kernels, support
+// 2) run through the same construction with the kernel swapped and every
+// "within 1" / "1/s" above doubled: 4 taps upsampling, about 4/s downsampling.
+// Only leading and trailing zero taps are trimmed (Catmull-Rom's zeros at
+// integer offsets stay inside a run); negative lobes are left to the encode's
+// clamp.  out == in is the identity for every filter -- this project's rule:
+// Mitchell and B-spline would blur at scale 1, and a crop-only plan must stay
+// an exact copy.
 #include "taps.h"
 
 #include <algorithm>
@@ -29,6 +37,43 @@ constexpr float kTiny = (float)1 / (1 << 20) / (1 << 20) / (1 << 20) / (1 << 20)
 inline float tent(float x) {
   x = x < 0.0f ? -x : x;
   return x <= 1.0f ? 1.0f - x : 0.0f;
+}
+
+// The cubic kernels of stb_image_resize2 (support 2), x = |distance|.  They
+// are evaluated in double at positions computed in double from the exact
+// scale out/in, then rounded to f32 once: their slope reaches 1.4, so the f32
+// position arithmetic the triangle path inherits from stbir (half an ulp of a
+// coordinate near 1000 is 3e-5) would cost several 1e-5 per weight.
+inline double catmullrom(double x) {
+  x = x < 0.0 ? -x : x;
+  if (x < 1.0) return 1.0 - x * x * (2.5 - 1.5 * x);
+  if (x < 2.0) return 2.0 - x * (4.0 + x * (0.5 * x - 2.5));
+  return 0.0;
+}
+
+inline double mitchell(double x) {
+  x = x < 0.0 ? -x : x;
+  if (x < 1.0) return (16.0 + x * x * (21.0 * x - 36.0)) / 18.0;
+  if (x < 2.0) return (32.0 + x * (-60.0 + x * (36.0 - 7.0 * x))) / 18.0;
+  return 0.0;
+}
+
+inline double cubicbspline(double x) {
+  x = x < 0.0 ? -x : x;
+  if (x < 1.0) return (4.0 + x * x * (3.0 * x - 6.0)) / 6.0;
+  if (x < 2.0) return (8.0 + x * (-12.0 + x * (6.0 - x))) / 6.0;
+  return 0.0;
+}
+
+// null: the triangle filter (tent, in stbir's f32 arithmetic)
+using Kernel = double (*)(double);
+Kernel kernel_of(int32_t filter) {
+  switch (filter) {
+    case kFilterCatmullRom: return catmullrom;
+    case kFilterMitchell: return mitchell;
+    case kFilterCubicBSpline: return cubicbspline;
+    default: return nullptr;
+  }
 }
 
 // A contiguous run of taps [n0, n1] with weights w[0..n1-n0].
@@ -94,19 +139,21 @@ void clamp_edges(Run& r, int32_t in) {
   }
 }
 
-std::vector<Run> upsample_runs(int32_t in, int32_t nbuild, float scale, float inv) {
+// k: the cubic kernel (null: triangle), sup: the support (triangle 1, cubics
+// 2), s: the exact scale out/in.
+std::vector<Run> upsample_runs(int32_t in, int32_t nbuild, float scale, float inv, Kernel k, float sup, double s) {
   std::vector<Run> runs(nbuild);
   for (int32_t n = 0; n < nbuild; n++) {
     const float centre = (float)n + 0.5f;
     const float src_centre = centre * inv;
-    int32_t first = (int32_t)std::floor((centre - scale) * inv + 0.5f);
-    int32_t last = (int32_t)std::floor((centre + scale) * inv - 0.5f);
+    int32_t first = (int32_t)std::floor((centre - scale * sup) * inv + 0.5f);
+    int32_t last = (int32_t)std::floor((centre + scale * sup) * inv - 0.5f);
     if (last < first) last = first;
     Run& r = runs[n];
     int32_t last_nz = -1;
     std::vector<float> w;
     for (int32_t px = first; px <= last; px++) {
-      float v = tent(src_centre - ((float)px + 0.5f));
+      float v = k ? (float)k(((double)n + 0.5) / s - ((double)px + 0.5)) : tent(src_centre - ((float)px + 0.5f));
       if (v < kTiny && v > -kTiny) {
         if (w.empty()) {  // leading zero taps are dropped
           first = px + 1;
@@ -127,15 +174,16 @@ std::vector<Run> upsample_runs(int32_t in, int32_t nbuild, float scale, float in
   return runs;
 }
 
-std::vector<Run> downsample_runs(int32_t in, int32_t out, int32_t nbuild, float scale, float inv) {
+std::vector<Run> downsample_runs(int32_t in, int32_t out, int32_t nbuild, float scale, float inv, Kernel k,
+                                 float sup, double s) {
   std::vector<Run> runs(nbuild);
   std::vector<char> seen(nbuild, 0);
-  const int32_t margin = ((int32_t)std::ceil(2.0f / scale)) / 2;
+  const int32_t margin = ((int32_t)std::ceil(2.0f * sup / scale)) / 2;
   for (int32_t px = -margin; px < in + margin; px++) {
     const float pc = (float)px + 0.5f;
     const float dst_centre = pc * scale;
-    int32_t o0 = (int32_t)std::floor((pc - inv) * scale + 0.5f);
-    int32_t o1 = (int32_t)std::floor((pc + inv) * scale - 0.5f);
+    int32_t o0 = (int32_t)std::floor((pc - inv * sup) * scale + 0.5f);
+    int32_t o1 = (int32_t)std::floor((pc + inv * sup) * scale - 0.5f);
     o0 = std::max(o0, 0);
     o1 = std::min(o1, out - 1);
     if (o0 > o1) continue;
@@ -144,7 +192,7 @@ std::vector<Run> downsample_runs(int32_t in, int32_t out, int32_t nbuild, float 
       o1 = std::min(o1, nbuild - 1);
     }
     for (int32_t o = o0; o <= o1; o++) {
-      float v = tent(((float)o + 0.5f) - dst_centre) * scale;
+      float v = k ? (float)(k(((double)o + 0.5) - ((double)px + 0.5) * s) * s) : tent(((float)o + 0.5f) - dst_centre) * scale;
       if (v < kTiny && v > -kTiny) v = 0.0f;
       Run& r = runs[o];
       if (!seen[o]) {
@@ -179,7 +227,8 @@ int32_t AxisTaps::hi() const {
   return v;
 }
 
-bool build_axis_taps(int32_t in, int32_t out, int32_t off, int32_t len, AxisTaps* t) {
+bool build_axis_taps(int32_t in, int32_t out, int32_t off, int32_t len, AxisTaps* t, int32_t filter) {
+  if (filter < 0 || filter >= kFilterCount) return false;
   if (in <= 0 || out <= 0 || len <= 0 || off < 0 || off + len > out) return false;
   t->in_size = in;
   t->out_size = out;
@@ -198,7 +247,10 @@ bool build_axis_taps(int32_t in, int32_t out, int32_t off, int32_t len, AxisTaps
     const int32_t g = std::gcd(out, in);
     const int32_t num = out / g, den = in / g;
     const int32_t nbuild = num < out ? num : out;
-    all = scale >= 1.0f ? upsample_runs(in, nbuild, scale, inv) : downsample_runs(in, out, nbuild, scale, inv);
+    const Kernel k = kernel_of(filter);
+    const float sup = filter == kFilterTriangle ? 1.0f : 2.0f;
+    all = scale >= 1.0f ? upsample_runs(in, nbuild, scale, inv, k, sup, s)
+                        : downsample_runs(in, out, nbuild, scale, inv, k, sup, s);
     for (auto& r : all) normalise(r);
     all.resize(out);
     for (int32_t n = nbuild; n < out; n++) {

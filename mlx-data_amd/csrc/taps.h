@@ -24,9 +24,20 @@ struct AxisTaps {
   int32_t hi() const;           // largest input index touched by the window
 };
 
+// Resampling filters (mxd_amd.h mxd_filter).  Triangle is what the reference
+// forces on stbir; the cubics are stbir's kernels of support 2.
+enum Filter : int32_t {
+  kFilterTriangle = 0,
+  kFilterCatmullRom = 1,
+  kFilterMitchell = 2,
+  kFilterCubicBSpline = 3,
+  kFilterCount = 4
+};
+
 // Builds taps for outputs [off, off+len) of an in_size -> out_size resize.
-// Returns false if the arguments are invalid.
-bool build_axis_taps(int32_t in_size, int32_t out_size, int32_t off, int32_t len, AxisTaps* out);
+// Returns false if the arguments (the filter included) are invalid.
+bool build_axis_taps(int32_t in_size, int32_t out_size, int32_t off, int32_t len, AxisTaps* out,
+                     int32_t filter = kFilterTriangle);
 
 // core::image::scale dims: lround(scale * w), lround(scale * h) in double.
 void smallest_side_dims(int64_t w, int64_t h, int64_t size, int64_t* tw, int64_t* th);

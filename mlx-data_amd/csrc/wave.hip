@@ -962,9 +962,37 @@ typename KernelOf<OUT>::type select_q(const WaveCfg& cfg) {
 // shapes of resize_smallest_side 256/512 from 200p..4K sources: downsampling
 // by the tent filter reaches each source row from at most two output rows
 // (S = 2), DMAX = ceil(in / out).
+//
+// wave_cubic.hip (MXD_WAVE_CUBIC_TU) compiles this file with another list:
+// the shapes of the cubic filters (support 2: a source row is reached from
+// about four output rows, S = 4; DMAX as for the tent; roughly twice the
+// horizontal taps), in the u8 and f32 modes, default load policy, RGB sources.
 template <int OUT>
 typename KernelOf<OUT>::type select_scatter(const WaveCfg& cfg) {
   if (cfg.channels != 3) return nullptr;
+#ifdef MXD_WAVE_CUBIC_TU
+  if (cfg.ycc || cfg.nt) return nullptr;  // RGB frames, default load policy
+#define MXD_CUBIC(D_, T_, Q_, P_)                                                                  \
+  if (cfg.s == 4 && cfg.dmax == D_ && cfg.taps == T_ && cfg.q == Q_ && cfg.p == P_)                \
+    return cfg.shift ? wave_kernel<3, P_, OUT, T_, Q_, kScatter, 4, D_, true>()                    \
+                     : wave_kernel<3, P_, OUT, T_, Q_, kScatter, 4, D_, false>();
+  // P = 4 at Q <= 2 and P = 8 (two strips where P = 4 needs three or more):
+  // DESIGN.md section 5g has the register figures behind the choice.
+  MXD_CUBIC(2, 6, 2, 4)    // 375 / 333 -> 256 (C4)
+  MXD_CUBIC(2, 6, 4, 8)
+  MXD_CUBIC(2, 8, 2, 4)    // 480 -> 256
+  MXD_CUBIC(2, 8, 4, 8)
+  MXD_CUBIC(3, 12, 2, 4)   // 720 -> 256
+  MXD_CUBIC(3, 12, 2, 8)
+  MXD_CUBIC(4, 17, 1, 4)   // 960 -> 256 (C2)
+  MXD_CUBIC(4, 17, 2, 8)
+  MXD_CUBIC(5, 17, 1, 4)   // 1080 -> 256, 2160 -> 512 (C5)
+  MXD_CUBIC(5, 17, 2, 8)
+  MXD_CUBIC(6, 24, 1, 4)   // 1440 -> 256
+  MXD_CUBIC(6, 24, 2, 8)
+#undef MXD_CUBIC
+  return nullptr;
+#else
 #define MXD_SCATTER(S_, D_, T_, Q_, P_)                                                           \
   if (cfg.s == S_ && cfg.dmax == D_ && cfg.taps == T_ && cfg.q == Q_ && cfg.p == P_)              \
     return cfg.ycc ? (P_ == 4 && !cfg.shift ? wave_kernel<3, 4, OUT, T_, Q_, kScatter, S_, D_, false, true>() \
@@ -1016,6 +1044,7 @@ typename KernelOf<OUT>::type select_scatter(const WaveCfg& cfg) {
 #undef MXD_SCATTER_B
 #undef MXD_SCATTER
   return nullptr;
+#endif  // MXD_WAVE_CUBIC_TU
 }
 
 // The kernel of cfg in one output mode (nullptr: none).
@@ -1034,17 +1063,20 @@ typename KernelOf<OUT>::type select_mode(const WaveCfg& cfg) {
   }
 }
 
-#ifndef MXD_WAVE_FMT_TU
+#if !defined(MXD_WAVE_FMT_TU) && !defined(MXD_WAVE_CUBIC_TU)
 WaveKernel select_kernel(const WaveCfg& cfg) {
   if (cfg.f32 == kOutFmt) return nullptr;  // wave_fmt.hip's kernels (launch_wave_fmt)
 #ifdef MXD_ONLY_C2
   return cfg.f32 ? select_mode<kOutF32>(cfg) : nullptr;
 #endif
-  return cfg.f32 ? select_mode<kOutF32>(cfg) : select_mode<kOutU8>(cfg);
+  const WaveKernel k = cfg.f32 ? select_mode<kOutF32>(cfg) : select_mode<kOutU8>(cfg);
+  return k ? k : reinterpret_cast<WaveKernel>(wave_cubic_kernel(cfg));  // wave_cubic.hip's shapes
 }
 #endif
 
+#ifndef MXD_WAVE_CUBIC_TU
 int lds_bytes(const WaveCfg& cfg) { return kWaves * wave_plane_floats(cfg.channels, cfg.p) * (int)sizeof(float); }
+#endif
 
 template <int C, int P>
 constexpr int plane_floats() {
@@ -1053,7 +1085,15 @@ constexpr int plane_floats() {
 
 }  // namespace
 
-#ifdef MXD_WAVE_FMT_TU
+#ifdef MXD_WAVE_CUBIC_TU
+// ---- wave_cubic.hip: the cubic filters' scatter shapes ---------------------
+void* wave_cubic_kernel(const WaveCfg& cfg) {
+  if (cfg.kind != kScatter || cfg.f32 == kOutFmt) return nullptr;
+  return reinterpret_cast<void*>(cfg.f32 ? select_scatter<kOutF32>(cfg) : select_scatter<kOutU8>(cfg));
+}
+
+}  // namespace mxd
+#elif defined(MXD_WAVE_FMT_TU)
 // ---- wave_fmt.hip: the formatted-output kernels and their launch ----------
 namespace {
 // the planes of the workgroup's waves, then the format table (one dword per entry)
@@ -1068,6 +1108,8 @@ int launch_wave_fmt(const WaveCfg& cfg, const ImgDev* imgs, const OutFmtDev& fmt
                      imgs, cfg.nimgs, cfg.nunits, cfg.per_img, cfg.prio, fmt);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+bool wave_fmt_has_kernel(const WaveCfg& cfg) { return select_mode<kOutFmt>(cfg) != nullptr; }
 
 int wave_fmt_capacity(const WaveCfg& cfg, int device) {
   const WaveFmtKernel k = select_mode<kOutFmt>(cfg);
@@ -1107,7 +1149,9 @@ int wave_plane_floats(int channels, int p) {
 
 int wave_lanes() { return kLanes; }
 
-bool wave_has_kernel(const WaveCfg& cfg) { return select_kernel(cfg) != nullptr; }
+bool wave_has_kernel(const WaveCfg& cfg) {
+  return cfg.f32 == kOutFmt ? wave_fmt_has_kernel(cfg) : select_kernel(cfg) != nullptr;
+}
 
 // Streaming copy: one 16-B load and store per thread, one block per 4 KiB
 // (no grid-stride loop): the form that measured fastest on MI355X
@@ -1186,7 +1230,7 @@ int wave_capacity(const WaveCfg& cfg, int device) {
 }  // namespace mxd
 
 #endif  // MXD_WAVE_FMT_TU
-#if MXD_STAMPS && !defined(MXD_WAVE_FMT_TU)
+#if MXD_STAMPS && !defined(MXD_WAVE_FMT_TU) && !defined(MXD_WAVE_CUBIC_TU)
 // Copies the first n units' (start, end) stamps of the last stamped launches.
 extern "C" int mxd_debug_stamps(unsigned long long* host, int n) {
   if (n > mxd::kMaxStamped) n = mxd::kMaxStamped;

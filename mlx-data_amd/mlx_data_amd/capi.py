@@ -19,11 +19,13 @@ MXD_ERR_DEVICE = 3
 MXD_ERR_NOMEM = 4
 MXD_U8 = 0
 MXD_F32_DIV255 = 1
+# enum mxd_filter, by the operator surface's names
+FILTERS = {"triangle": 0, "catmullrom": 1, "mitchell": 2, "cubicbspline": 3}
 
 # Every symbol include/mxd_amd.h declares.
 EXPORTS = (
     "mxd_abi_version", "mxd_last_error", "mxd_device_count", "mxd_device_properties",
-    "mxd_resize_smallest_side_dims", "mxd_center_crop_origin", "mxd_axis_taps",
+    "mxd_resize_smallest_side_dims", "mxd_center_crop_origin", "mxd_axis_taps", "mxd_axis_taps_filter",
     "mxd_resize_crop_batch", "mxd_set_kernel_policy", "mxd_set_tuning", "mxd_describe_plan",
     "mxd_describe_band_plan", "mxd_copy_bandwidth",
     "mxd_set_device", "mxd_malloc_device", "mxd_free_device", "mxd_malloc_pinned", "mxd_free_pinned",
@@ -97,7 +99,7 @@ class MxdImage(ctypes.Structure):
         ("dst", ctypes.c_void_p),
         ("dst_stride", ctypes.c_int64),
         ("rgba_weighted", ctypes.c_int32),
-        ("reserved", ctypes.c_int32),
+        ("filter", ctypes.c_int32),
     ]
 
 
@@ -134,7 +136,7 @@ class MxdJpegImage(ctypes.Structure):
         ("crop_w", ctypes.c_int32),
         ("crop_h", ctypes.c_int32),
         ("flip", ctypes.c_int32),
-        ("reserved", ctypes.c_int32),
+        ("filter", ctypes.c_int32),
         ("dst", ctypes.c_void_p),
         ("dst_stride", ctypes.c_int64),
     ]
@@ -204,22 +206,29 @@ def center_crop_origin(w, h, cw, ch):
     return x.value, y.value
 
 
-def axis_taps(in_size, out_size, off=0, length=None):
-    """(first[len], ntaps[len], weights[len, width]) of the product tap builder."""
+def axis_taps(in_size, out_size, off=0, length=None, filter=0):
+    """(first[len], ntaps[len], weights[len, width]) of the product tap builder
+    (filter: an mxd_filter value or its name; 0 goes through mxd_axis_taps)."""
     length = out_size - off if length is None else length
+    filter = FILTERS.get(filter, filter)
     need = ctypes.c_int32()
     L = lib()
-    rc = L.mxd_axis_taps(in_size, out_size, off, length, 0, None, None, None, ctypes.byref(need))
+
+    def call(width, first, cnt, w, needed):
+        if filter == 0:
+            return L.mxd_axis_taps(in_size, out_size, off, length, width, first, cnt, w, needed)
+        return L.mxd_axis_taps_filter(in_size, out_size, off, length, int(filter), width, first, cnt, w, needed)
+
+    rc = call(0, None, None, None, ctypes.byref(need))
     width = need.value
     if rc != MXD_OK and width <= 0:
         check(rc)
     first = np.zeros(length, np.int32)
     cnt = np.zeros(length, np.int32)
     w = np.zeros((length, width), np.float32)
-    check(L.mxd_axis_taps(in_size, out_size, off, length, width,
-                          first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                          cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                          w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), None))
+    check(call(width, first.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+               cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+               w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), None))
     return first, cnt, w
 
 

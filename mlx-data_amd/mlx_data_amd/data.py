@@ -50,6 +50,16 @@ arrays; bfloat16 has no NumPy type, so a host batch of it (and
 ``DeviceArray.numpy()``) raises ``RuntimeError``: use ``device=`` and
 ``torch.from_dlpack``.
 
+``image_resize(key, w, h, output_key="", *, filter="triangle")`` and
+``image_resize_smallest_side(key, size, output_key="", *, filter="triangle")``
+(and their ``_if`` forms) take the resampling filter of the resize:
+``"triangle"`` (mlx-data's, the default), ``"catmullrom"`` (PIL ``BICUBIC``,
+torch ``bicubic`` with ``antialias=True``), ``"mitchell"`` or
+``"cubicbspline"``.  An unknown name raises ``ValueError`` when the op is made.
+A pending image carries the filter of its one resize (a second resize
+materialises the first); a resize to the size the image already has is the
+identity for every filter.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole

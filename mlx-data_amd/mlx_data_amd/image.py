@@ -32,13 +32,16 @@ def plan_resize_smallest_side_center_crop(w, h, size, cw, ch):
     return tw, th, x, y
 
 
-def resize_crop(images, geoms, out_dtype="uint8", device=0):
+def resize_crop(images, geoms, out_dtype="uint8", device=0, filter="triangle"):
     """Host-resident fused path.
 
     images: list of (H, W, C) uint8 arrays.
     geoms:  list of (resize_w, resize_h, crop_x, crop_y, crop_w, crop_h, flip).
+    filter: "triangle" (the reference's), "catmullrom", "mitchell" or "cubicbspline".
     Returns a list of (crop_h, crop_w, C) arrays (uint8, or float32 q/255).
     """
+    if filter not in capi.FILTERS:
+        raise ValueError(f"unknown filter {filter!r} (one of {', '.join(capi.FILTERS)})")
     f32 = out_dtype in ("float32", np.float32)
     outs, entries = [], []
     keep = []
@@ -50,19 +53,20 @@ def resize_crop(images, geoms, out_dtype="uint8", device=0):
         outs.append(out)
         entries.append(dict(src=img.ctypes.data, src_stride=img.strides[0], src_w=img.shape[1], src_h=img.shape[0],
                             channels=img.shape[2], resize_w=rw, resize_h=rh, crop_x=x, crop_y=y, crop_w=cw,
-                            crop_h=ch, flip=int(bool(flip)), dst=out.ctypes.data, dst_stride=out.strides[0]))
+                            crop_h=ch, flip=int(bool(flip)), dst=out.ctypes.data, dst_stride=out.strides[0],
+                            filter=capi.FILTERS[filter]))
     arr, n = capi.make_images(entries)
     capi.resize_crop_host(arr, n, capi.MXD_F32_DIV255 if f32 else capi.MXD_U8, device)
     return outs
 
 
-def resize_smallest_side_center_crop(images, size, cw, ch, out_dtype="uint8", device=0):
+def resize_smallest_side_center_crop(images, size, cw, ch, out_dtype="uint8", device=0, filter="triangle"):
     geoms = []
     for img in images:
         h, w = img.shape[:2]
         tw, th, x, y = plan_resize_smallest_side_center_crop(w, h, size, cw, ch)
         geoms.append((tw, th, x, y, cw, ch, 0))
-    return resize_crop(images, geoms, out_dtype, device)
+    return resize_crop(images, geoms, out_dtype, device, filter)
 
 
 def _pixmap(images, op, params_of, dims_of, out_c, device):
