@@ -54,9 +54,14 @@ extern "C" {
  * resampling filters -- mxd_filter, mxd_image::filter and
  * mxd_jpeg_image::filter (the former `reserved` fields: same layout, 0 =
  * triangle keeps every zero-initialising caller as it was), and
- * mxd_axis_taps_filter. */
+ * mxd_axis_taps_filter.
+ * 7, added without a new number (test for MXD_HAS_COLOR / the symbols): the
+ * per-image colour transform -- mxd_color, mxd_color_twist_matrix,
+ * mxd_color_apply_u8, mxd_resize_crop_batch_color,
+ * mxd_resize_crop_to_device_color, mxd_jpeg_resize_crop_to_device_color. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
+#define MXD_HAS_COLOR 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -501,6 +506,56 @@ int mxd_resize_crop_batch_fmt(const mxd_image* images, int32_t n, const mxd_out_
 int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device);
 int mxd_jpeg_resize_crop_to_device_fmt(const mxd_jpeg_image* images, int32_t n, const mxd_out_format* fmt,
                                        int32_t device);
+
+/* ---- per-image colour transform (ABI 7 additions; feature test: MXD_HAS_COLOR)
+ *
+ * A 3 x 4 affine map of an RGB pixel's result bytes q0, q1, q2 (exactly what
+ * MXD_U8 gives: the resize arithmetic is untouched).  For channel c, in
+ * float32 operations each correctly rounded, none fused:
+ *
+ *   v   = ((m[c][0]*q0 + m[c][1]*q1) + m[c][2]*q2) + m[c][3]
+ *   q'c = (uint8) trunc(clamp(v + 0.5f, 0, 255))
+ *
+ * m[c][3] is in byte units.  Everything downstream reads q' where it read q:
+ * the u8 output, the exact q'/255 and the mxd_out_format table.  Brightness,
+ * fixed-centre contrast, saturation and hue rotation are such matrices
+ * (mxd_color_twist_matrix); so are a channel swap, sepia or grey in three
+ * channels.  Entries must be finite with |m| <= 1e6; an entry with
+ * |m| < 2^-100 acts as zero.  The identity returns q exactly. */
+typedef struct mxd_color {
+  float m[3][4];
+} mxd_color;
+
+/* Host only: M = B(brightness) . C(contrast) . S(saturation) . H(hue) for a
+ * column vector [r g b 1] in [0, 1] units, built in double and rounded to
+ * float once, the offset column multiplied by 255 first.  H rotates the I and
+ * Q rows of the YIQ transform by hue_degrees; S(s) = s I + (1 - s) 1 w^T with w
+ * the luma row; C(c) scales by c about 0.5; B(b) scales everything by b.  A
+ * factor at its default (1, 1, 1, 0) contributes no matrix, so the defaults
+ * give exactly the identity.  MXD_ERR_INVALID for a negative or non-finite
+ * brightness, contrast or saturation, or a non-finite hue. */
+int mxd_color_twist_matrix(double brightness, double contrast, double saturation, double hue_degrees, mxd_color* out);
+
+/* Host only: the CPU statement of the arithmetic above on npixels packed RGB
+ * pixels (out may equal rgb). */
+int mxd_color_apply_u8(const uint8_t* rgb, int64_t npixels, const mxd_color* color, uint8_t* out);
+
+/* mxd_resize_crop_batch / mxd_resize_crop_to_device /
+ * mxd_jpeg_resize_crop_to_device with colors[i] applied to images[i]'s result.
+ * fmt == NULL: the output is out_dtype's (MXD_U8 / MXD_F32_DIV255; f32
+ * destinations and strides must be multiples of 4 bytes); else the formatted
+ * output of the _fmt calls, with every check of theirs, and out_dtype is not
+ * read.  Device destinations only.  MXD_ERR_INVALID (the message names the
+ * image and the field) for a null colors, a non-finite or too large entry, or
+ * channels != 3.  Every image is resized as a u8 image into a scratch by the
+ * kernels of the plain calls; one more launch on the same stream applies the
+ * matrices and writes every destination. */
+int mxd_resize_crop_batch_color(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                const mxd_out_format* fmt, int32_t device, void* stream);
+int mxd_resize_crop_to_device_color(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                    const mxd_out_format* fmt, int32_t device);
+int mxd_jpeg_resize_crop_to_device_color(const mxd_jpeg_image* images, const mxd_color* colors, int32_t n,
+                                         int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
 
 /* Diagnostics: where a host-side pipeline's time goes, summed over every
  * thread since the last reset (reset != 0 zeroes them after reading).

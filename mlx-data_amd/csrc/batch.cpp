@@ -331,13 +331,16 @@ int validate_batch(const mxd_image* images, int32_t n, int32_t* out_dtype, int32
 
 // Formatted call: the format as the kernels see it and, when some image takes
 // two passes, the stream's scratch (held until the last launch is enqueued)
-// with the layout's scratch offsets made addresses in it.
-int take_scratch(BatchLayout& L, const mxd_out_format& fmt, int32_t device, void* stream, mxd::OutFmtDev* ofd,
+// with the layout's scratch offsets made addresses in it.  fmt == nullptr (a
+// colour call with u8 output): no table.
+int take_scratch(BatchLayout& L, const mxd_out_format* fmt, int32_t device, void* stream, mxd::OutFmtDev* ofd,
                  std::unique_lock<std::mutex>* hold) {
-  ofd->plane_stride = fmt.plane_stride;
-  ofd->elem16 = fmt_elem_size(fmt) == 2 ? 1 : 0;
-  ofd->chw = fmt.layout == MXD_LAYOUT_CHW ? 1 : 0;
-  if (int rc = fmt_device_table(device, fmt, L.images[0].channels, &ofd->table)) return rc;
+  if (fmt) {
+    ofd->plane_stride = fmt->plane_stride;
+    ofd->elem16 = fmt_elem_size(*fmt) == 2 ? 1 : 0;
+    ofd->chw = fmt->layout == MXD_LAYOUT_CHW ? 1 : 0;
+    if (int rc = fmt_device_table(device, *fmt, L.images[0].channels, &ofd->table)) return rc;
+  }
   if (L.scratch_bytes == 0) return MXD_OK;
   FmtScratch* sc = fmt_scratch(device, stream);
   *hold = std::unique_lock<std::mutex>(sc->mu);
@@ -404,23 +407,28 @@ int launch_all(const BatchLayout& L, const ImgDev* dev, Workspace* ws, const mxd
 
 // One launchable batch: its layout, the upload, the launches.
 int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-                   const Stored* stored, const mxd_out_format* fmt) {
+                   const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors) {
   DeviceGuard guard(device);
   BatchLayout L;
-  if (int rc = build_layout(device_env(), device, images, n, stored, out_dtype, fmt, &L)) return rc;
+  if (int rc = build_layout(device_env(), device, images, n, stored, out_dtype, fmt, &L, colors)) return rc;
   mxd::OutFmtDev ofd{};
   std::unique_lock<std::mutex> scratch_hold;
-  if (fmt)
-    if (int rc = take_scratch(L, *fmt, device, stream, &ofd, &scratch_hold)) return rc;
+  if (fmt || colors)
+    if (int rc = take_scratch(L, fmt, device, stream, &ofd, &scratch_hold)) return rc;
   ImgDev* dev = nullptr;
   std::unique_lock<std::mutex> hold;
   Workspace* ws = nullptr;
   bool hit = false;
   if (int rc = upload_descs(L.descs, device, stream, &dev, &hold, &ws, &hit)) return rc;
-  int launch_rc = launch_all(L, dev, ws, fmt ? &ofd : nullptr, stream);
+  // (a colour call's resize kernels run in their u8 mode: the format is color_rows')
+  int launch_rc = launch_all(L, dev, ws, fmt && !colors ? &ofd : nullptr, stream);
   // The second pass of a formatted call, behind the joins: every resize
   // kernel that wrote scratch rows is ordered before it on the caller's stream.
-  if (launch_rc == MXD_OK && L.fmt_count > 0 &&
+  if (launch_rc == MXD_OK && colors) {
+    if (mxd::launch_color_rows(reinterpret_cast<const mxd::ColorRowDev*>(dev + L.fmt_at), L.fmt_count, L.fmt_blocks, ofd,
+                               stream))
+      launch_rc = fail(MXD_ERR_DEVICE, std::string("color_rows launch failed: ") + hipGetErrorString(hipGetLastError()));
+  } else if (launch_rc == MXD_OK && L.fmt_count > 0 &&
       mxd::launch_format_rows(reinterpret_cast<const mxd::FmtRowDev*>(dev + L.fmt_at), L.fmt_count, L.fmt_blocks, ofd,
                               stream))
     launch_rc = fail(MXD_ERR_DEVICE, std::string("format_rows launch failed: ") + hipGetErrorString(hipGetLastError()));
@@ -446,14 +454,19 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 }
 
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored, const mxd_out_format* fmt) {
+              const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors) {
+  mxd_out_format f32_fmt;
+  if (colors)
+    if (int rc = color_prepare(images, colors, n, &out_dtype, &fmt, &f32_fmt)) return rc;
   if (int rc = validate_batch(images, n, &out_dtype, device, fmt)) return rc;
   if (n == 0) return MXD_OK;
-  const std::vector<SubBatch> subs = split_batch(images, n, stored);
-  if (subs.empty()) return run_launchable(images, n, out_dtype, device, stream, stored, fmt);
+  // (a colour call's images all have three channels: one launchable batch,
+  // so colors[i] stays beside images[i])
+  const std::vector<SubBatch> subs = colors ? std::vector<SubBatch>{} : split_batch(images, n, stored);
+  if (subs.empty()) return run_launchable(images, n, out_dtype, device, stream, stored, fmt, colors);
   for (const SubBatch& s : subs)
     if (int rc = run_launchable(s.images.data(), (int32_t)s.images.size(), out_dtype, device, stream,
-                                stored ? s.stored.data() : nullptr, fmt))
+                                stored ? s.stored.data() : nullptr, fmt, nullptr))
       return rc;
   return MXD_OK;
 }

@@ -334,11 +334,22 @@ void place_formatted(Batch& b, const mxd_image* callers) {
   b.L.scratch_bytes = at;
 }
 
+// Colour call: every image's rows go to the scratch.
+void place_colored(Batch& b) {
+  size_t at = 0;
+  for (int32_t i = 0; i < b.n; i++) {
+    mxd_image& im = b.L.images[i];
+    im.dst = reinterpret_cast<void*>(at);
+    at += scratch_size(im);
+  }
+  b.L.scratch_bytes = at;
+}
+
 // After every descriptor, in ImgDev-sized blocks: the unit -> image tables of
 // the band launches whose images differ in unit count (int32 each), then
 // format_rows' entries: part of the upload's bytes, so a cached slot is
 // reused only with the same scratch rows and destinations.
-void append_tables(Batch& b, const mxd_image* callers) {
+void append_tables(Batch& b, const mxd_image* callers, const mxd_color* colors) {
   BatchLayout& L = b.L;
   std::vector<int32_t> unit_tables;
   for (BatchLayout::BandGroup& g : L.bands) {
@@ -355,6 +366,24 @@ void append_tables(Batch& b, const mxd_image* callers) {
   if (!unit_tables.empty())
     std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.tables_at), unit_tables.data(), unit_tables.size() * 4);
   L.fmt_at = L.descs.size();
+  if (colors) {
+    // color_rows' entries, in batch order: the matrices are part of the
+    // upload's bytes, so a cached slot is reused only for the same matrices.
+    std::vector<mxd::ColorRowDev> rows(b.n);
+    for (int32_t i = 0; i < b.n; i++) {
+      const mxd_image& im = L.images[i];
+      mxd::ColorRowDev& r = rows[i];
+      r = mxd::ColorRowDev{static_cast<const uint8_t*>(im.dst), callers[i].dst, im.dst_stride, callers[i].dst_stride,
+                           im.crop_w, im.crop_h, im.channels, L.fmt_blocks, {}};
+      for (int k = 0; k < 12; k++) r.m[k] = color_entry(colors[i].m[k / 4][k % 4]);
+      L.fmt_blocks += (im.crop_h + mxd::kColorRows - 1) / mxd::kColorRows;
+    }
+    L.fmt_count = b.n;
+    const size_t bytes = rows.size() * sizeof(mxd::ColorRowDev);
+    L.descs.resize(L.fmt_at + (bytes + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+    std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.fmt_at), rows.data(), bytes);
+    return;
+  }
   if (!b.formatted) return;
   std::vector<mxd::FmtRowDev> rows;
   for (int32_t i = 0; i < b.n; i++) {
@@ -379,21 +408,29 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity) {
 
 void BatchLayout::add_scratch(uint8_t* base) {
   for (int32_t k = 0; k < n; k++)
-    if (!plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
+    if (colored || !plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
+  if (colored) {
+    for (int32_t j = 0; j < fmt_count; j++)
+      color_rows()[j].src = base + reinterpret_cast<uintptr_t>(color_rows()[j].src);
+    return;
+  }
   for (int32_t j = 0; j < fmt_count; j++) fmt_rows()[j].src = base + reinterpret_cast<uintptr_t>(fmt_rows()[j].src);
 }
 
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
-                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out) {
+                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors) {
   *out = BatchLayout{};
   BatchLayout& L = *out;
   L.n = n;
+  L.colored = colors != nullptr;
   // A formatted call plans its kernels as a u8 call does: the wave kernels
   // exist in the same shapes in every output mode and write any element
   // alignment, and an image they do not take is resized into u8 scratch rows
   // (16-byte aligned; placed once the plans are known).
   const mxd_image* const callers = images;
-  if (fmt) {
+  // A colour call plans every image so, and keeps every u8 kernel a plain u8
+  // call has (the cubic filters' and JPEG plane sources' wave kernels too).
+  if (fmt || colors) {
     out_dtype = MXD_U8;
     L.images.assign(images, images + n);
     for (mxd_image& im : L.images) {
@@ -402,9 +439,10 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
     }
     images = L.images.data();
   }
-  Batch b{env, device, images, stored, n, images[0].channels, out_dtype, fmt != nullptr, L, {}};
+  Batch b{env, device, images, stored, n, images[0].channels, out_dtype, fmt != nullptr && !colors, L, {}};
   if (int rc = plan_images(b)) return rc;
-  if (fmt) place_formatted(b, callers);
+  if (colors) place_colored(b);
+  else if (fmt) place_formatted(b, callers);
   // Descriptors of one upload: band-kernel images first, then wave-kernel
   // images, then the general kernel's.
   L.descs.resize(n);
@@ -412,7 +450,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = band_groups(b)) return rc;
   if (int rc = wave_groups(b)) return rc;
   if (int rc = general_group(b)) return rc;
-  append_tables(b, callers);
+  append_tables(b, callers, colors);
   // Largest first (a band unit is a workgroup, ~4 wave units).
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});

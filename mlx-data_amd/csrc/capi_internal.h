@@ -296,13 +296,21 @@ struct BatchLayout {
   size_t scratch_bytes = 0;
   int32_t fmt_count = 0, fmt_blocks = 0;
   mxd::FmtRowDev* fmt_rows() { return reinterpret_cast<mxd::FmtRowDev*>(descs.data() + fmt_at); }
+  // Colour call: every image is resized into u8 scratch rows (wave kernels in
+  // their u8 mode included) and color_rows writes every destination.  Its
+  // entries, one per image in batch order with the image's matrix, take
+  // format_rows' place from fmt_at (fmt_count of them, fmt_blocks workgroups).
+  bool colored = false;
+  mxd::ColorRowDev* color_rows() { return reinterpret_cast<mxd::ColorRowDev*>(descs.data() + fmt_at); }
   const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
   void add_scratch(uint8_t* base);
 };
 // fmt != nullptr: a formatted call (out_dtype is not read; the format's values
-// are launch arguments, not part of the layout).
+// are launch arguments, not part of the layout).  colors != nullptr: a colour
+// call (colors[i] belongs to images[i]; planned as a u8 call into scratch
+// whatever fmt and out_dtype say: the output form is color_rows' alone).
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
-                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out);
+                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors = nullptr);
 
 // The images of a batch for which pred holds, in batch order, with their
 // stored entries.
@@ -332,8 +340,23 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 // kernel takes are written in that form by the resize launch; the others are
 // resized into a per-(device, stream) u8 scratch and formatted by one
 // format_rows launch that follows on the stream.
+// colors != nullptr: a colour call; fmt == nullptr then means out_dtype's form
+// (MXD_U8 / MXD_F32_DIV255).  Every image is resized into the scratch in u8
+// and one color_rows launch writes the destinations.
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored = nullptr, const mxd_out_format* fmt = nullptr);
+              const Stored* stored = nullptr, const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr);
+
+// ---------------------------------------------------------------------------
+// Colour transform (color.cpp).
+// An entry as the kernels and the CPU statement use it: |m| < 2^-100 is zero.
+float color_entry(float m);
+// colors[i] against images[i] (images may be null: the matrices alone).
+int color_validate(const mxd_image* images, const mxd_color* colors, int32_t n);
+// The head of every colour call: validates the matrices, makes *fmt the
+// format color_rows writes (f32_fmt, the q / 255 table, for MXD_F32_DIV255;
+// null stays null for MXD_U8) and *out_dtype the form the kernels are planned in.
+int color_prepare(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t* out_dtype,
+                  const mxd_out_format** fmt, mxd_out_format* f32_fmt);
 
 // ---------------------------------------------------------------------------
 // Formatted outputs (outfmt.cpp).
@@ -351,10 +374,13 @@ int fmt_device_table(int32_t device, const mxd_out_format& fmt, int32_t channels
 // Host-resident batches (hostpath.cpp; JPEG batches: hostjpeg.cpp; what
 // those two share is in hostpath.h).
 // fmt != nullptr (device destinations only): every chunk's launch writes that format.
+// colors != nullptr (device destinations only): every chunk's launch is a
+// colour call with the chunk's slice of the matrices.
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_jpeg_image* jpeg = nullptr, const mxd_out_format* fmt = nullptr);
+              const mxd_jpeg_image* jpeg = nullptr, const mxd_out_format* fmt = nullptr,
+              const mxd_color* colors = nullptr);
 int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_out_format* fmt = nullptr);
+              const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr);
 // mxd_host_stats counters: host-path calls, images, wall ns, device-wait ns,
 // coefficient parses, parse ns
 extern std::atomic<int64_t> g_host_stats[6];

@@ -117,6 +117,9 @@ struct HostCall {
   // not null: every chunk's launch writes this format into the (device)
   // destinations; out_dtype is then MXD_U8, the form the kernels are planned in
   const mxd_out_format* fmt = nullptr;
+  // not null: a colour call; colors[i] belongs to images[i], and a chunk's
+  // launch gets the slice of its range
+  const mxd_color* colors = nullptr;
   std::vector<Stage> st;
   std::vector<ChunkRange> chunks;
   HostCtx* ctx = nullptr;

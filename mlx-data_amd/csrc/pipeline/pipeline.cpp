@@ -261,16 +261,37 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
   std::vector<mxd_image> plain;
   std::vector<mxd_jpeg_image> jp;
   std::vector<std::shared_ptr<const JpegSource>> keep;  // alive for the call
+  std::vector<mxd_color> pc, jc;  // the colours of `plain` and `jp`, image for image
+  bool colored = false;
   for (size_t i = 0; i < n; i++) {
     const Job& j = jobs[i];
+    mxd_color c;
+    std::memcpy(c.m, j.plan.color.data(), sizeof c.m);
+    colored = colored || j.plan.colored;
     if (auto src = j.plan.src->jpeg()) {
       jp.push_back(jpeg_desc(j.plan, *src, j.dst, j.stride));
+      jc.push_back(c);
       keep.push_back(std::move(src));
     } else {
       plain.push_back(plan_desc(j.plan, j.dst, j.stride));
+      pc.push_back(c);
     }
   }
   g_run_jpeg.fetch_add((int64_t)jp.size());
+  // Some plan is coloured: the whole launch goes through the _color calls,
+  // plans without a colour with the identity (exact).  Device destinations only.
+  if (colored) {
+    if (!dst_device) throw std::logic_error("mxd: a colour launch needs device destinations");
+    mxd_out_format of{};
+    if (fmt) of = abi_format(*fmt, jobs[0]);
+    if (!jp.empty())
+      if (int rc = mxd_jpeg_resize_crop_to_device_color(jp.data(), jc.data(), (int32_t)jp.size(), dtype,
+                                                        fmt ? &of : nullptr, device))
+        return rc;
+    if (plain.empty()) return MXD_OK;
+    return mxd_resize_crop_to_device_color(plain.data(), pc.data(), (int32_t)plain.size(), dtype, fmt ? &of : nullptr,
+                                           device);
+  }
   if (fmt) {
     // formatted outputs: device destinations only (mxd_*_to_device_fmt)
     if (!dst_device || n == 0) return MXD_OK;
@@ -380,42 +401,59 @@ namespace {
 // message wins.
 std::shared_ptr<void> device_block(int device, int64_t bytes);  // from the device batch pool (below)
 
-// Formatted results bound for host memory, the first version's simple route:
-// the _fmt calls write device destinations only, so the jobs run into a block
-// of the device batch pool laid out like their host destinations and one
-// mxd_memcpy_d2h brings it back (one per job when the destinations are not one
-// dense range).  No chunk overlap between the kernels and the copy.  Returns
-// the error message, empty when all went well.
-std::string run_formatted_to_host(const Job* jobs, size_t n, int device, const OutFormat& fmt) {
+// Results that only a device call can write, bound for host memory -- the
+// formatted outputs (the _fmt calls) and every output of a colour launch (the
+// _color calls) have device destinations only: the jobs run into a block of
+// the device batch pool, each image dense in it, and one mxd_memcpy_d2h brings
+// the block back -- straight into place when the host destinations are one
+// dense range laid out the same way, else through a host copy of the block
+// (rows copied out to each job's stride).  fmt == nullptr: dtype's form (u8 /
+// f32).  No chunk overlap between the kernels and the copy.  Returns the error
+// message, empty when all went well.
+std::string run_formatted_to_host(const Job* jobs, size_t n, int device, int32_t dtype, const OutFormat* fmt) {
   if (n == 0) return std::string();
   try {
-    const int64_t es = fmt.elem == MXD_ELEM_F32 ? 4 : 2;
-    std::vector<int64_t> bytes(n);
+    const int64_t es = fmt ? (fmt->elem == MXD_ELEM_F32 ? 4 : 2) : dtype == MXD_F32_DIV255 ? 4 : 1;
+    std::vector<int64_t> bytes(n), row(n);
     auto* lo = static_cast<uint8_t*>(jobs[0].dst);
     auto* hi = lo;
     int64_t sum = 0;
+    bool packed = true;  // every job's rows as dense in the host destination as in the block
     for (size_t i = 0; i < n; i++) {
-      bytes[i] = jobs[i].plan.crop_h * jobs[i].plan.crop_w * jobs[i].plan.channels() * es;
+      const ImagePlan& p = jobs[i].plan;
+      row[i] = p.crop_w * (fmt && fmt->chw() ? 1 : p.channels()) * es;
+      bytes[i] = p.crop_h * p.crop_w * p.channels() * es;
+      packed = packed && jobs[i].stride == row[i];
       auto* d = static_cast<uint8_t*>(jobs[i].dst);
       lo = std::min(lo, d);
       hi = std::max(hi, d + bytes[i]);
       sum += bytes[i];
     }
-    const bool dense = hi - lo == sum;
+    const bool dense = packed && hi - lo == sum;
     std::shared_ptr<void> block = device_block(device, sum);
     auto* base = static_cast<uint8_t*>(block.get());
     std::vector<Job> dev(jobs, jobs + n);
     int64_t at = 0;
     for (size_t i = 0; i < n; i++) {
       dev[i].dst = base + (dense ? static_cast<uint8_t*>(jobs[i].dst) - lo : at);
+      dev[i].stride = row[i];
       at += bytes[i];
     }
-    if (run_on(dev.data(), n, MXD_U8, device, true, &fmt) != MXD_OK) return mxd_last_error();
+    if (run_on(dev.data(), n, dtype, device, true, fmt) != MXD_OK) return mxd_last_error();
     if (dense) {
       if (mxd_memcpy_d2h(lo, base, (size_t)sum, device) != MXD_OK) return mxd_last_error();
-    } else {
+    } else if (packed) {
       for (size_t i = 0; i < n; i++)
         if (mxd_memcpy_d2h(jobs[i].dst, dev[i].dst, (size_t)bytes[i], device) != MXD_OK) return mxd_last_error();
+    } else {
+      std::vector<uint8_t> host((size_t)sum);
+      if (mxd_memcpy_d2h(host.data(), base, (size_t)sum, device) != MXD_OK) return mxd_last_error();
+      at = 0;
+      for (size_t i = 0; i < n; i++) {
+        for (int64_t r = 0; r < jobs[i].plan.crop_h; r++)
+          std::memcpy(static_cast<uint8_t*>(jobs[i].dst) + r * jobs[i].stride, host.data() + at + r * row[i], row[i]);
+        at += bytes[i];
+      }
     }
   } catch (const std::exception& ex) {
     return ex.what();
@@ -430,10 +468,15 @@ void run_host(const std::vector<Job>& jobs, int32_t dtype, const OutFormat* fmt 
   const size_t n = jobs.size();
   const size_t k = (size_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)devs.size(), (int64_t)n / kMinSliceImages));
   const std::vector<Slice> sl = split_batch((int64_t)n, (int64_t)devs.size(), g_rr.fetch_add(k));
-  auto slice = [&jobs, dtype, &devs, &sl, fmt](size_t s) -> std::string {
+  // a coloured plan anywhere: every slice takes the device call and one copy
+  // back, like a formatted batch (each slice carries its own jobs' matrices)
+  bool colored = false;
+  for (const Job& j : jobs) colored = colored || j.plan.colored;
+  auto slice = [&jobs, dtype, &devs, &sl, fmt, colored](size_t s) -> std::string {
     const Job* first = jobs.data() + sl[s].begin;
     const size_t count = (size_t)(sl[s].end - sl[s].begin);
-    if (fmt) return run_formatted_to_host(first, count, devs[sl[s].device], *fmt);  // every slice the same format
+    if (fmt || colored)  // (every slice the same format)
+      return run_formatted_to_host(first, count, devs[sl[s].device], fmt ? MXD_U8 : dtype, fmt);
     if (run_on(first, count, dtype, devs[sl[s].device], false) != MXD_OK)
       return mxd_last_error();  // thread-local: read on the failing thread
     return std::string();
@@ -627,7 +670,7 @@ std::shared_ptr<Array> plan_resize(const std::shared_ptr<Array>& img, int64_t dw
   // (an alpha-weighted same-size resize is not the identity: it zeroes the
   // colour of transparent pixels, so it runs before the next one)
   const bool identity_so_far =
-      p.resize_w == p.sw && p.resize_h == p.sh && !p.flip && !(p.resampled && p.channels() == 4);
+      p.resize_w == p.sw && p.resize_h == p.sh && !p.flip && !(p.resampled && p.channels() == 4) && !p.colored;
   if (identity_so_far) {
     // crop-then-resize: the crop becomes the source window.
     p.sx += p.crop_x;
@@ -864,6 +907,84 @@ std::shared_ptr<Array> ImageNormalize::apply_image(const std::shared_ptr<Array>&
 std::shared_ptr<Array> ImageNormalize::apply_video(const std::shared_ptr<Array>& video) const {
   if (fmt_.chw()) throw std::runtime_error("image_normalize: layout chw takes (H, W, C) images, not (F, H, W, C) videos");
   return ImageOp::apply_video(video);
+}
+
+// ---- colour ops: mark the plan -------------------------------------------------
+namespace {
+std::shared_ptr<Array> plan_color(const std::shared_ptr<Array>& img, const std::array<float, 12>& m) {
+  if (img->shape(2) != 3)
+    throw std::runtime_error("image_color_twist: image must have 3 channels, not " + std::to_string(img->shape(2)));
+  ImagePlan p = view(img);
+  if (p.colored) {
+    // a second colour op: run the first, map its bytes (each op rounds to bytes)
+    img->data();
+    p = view(img);
+  }
+  p.colored = true;
+  p.color = m;
+  return make(p);
+}
+}  // namespace
+
+ImageColorMatrix::ImageColorMatrix(std::string ikey, const std::array<float, 12>& matrix, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), m_(matrix) {
+  for (float v : m_)
+    if (!std::isfinite(v) || std::fabs(v) > 1e6f)
+      throw std::invalid_argument("image_color_matrix: entries must be finite and at most 1e6 in magnitude");
+}
+
+std::shared_ptr<Array> ImageColorMatrix::apply_image(const std::shared_ptr<Array>& img) const {
+  return plan_color(img, m_);
+}
+
+std::array<float, 12> color_twist(double brightness, double contrast, double saturation, double hue) {
+  mxd_color c;
+  if (mxd_color_twist_matrix(brightness, contrast, saturation, hue, &c) != MXD_OK) {
+    std::string msg = mxd_last_error();
+    const std::string prefix = "mxd_color_twist_matrix: ";
+    if (msg.compare(0, prefix.size(), prefix) == 0) msg = msg.substr(prefix.size());
+    throw std::invalid_argument("image_color_twist: " + msg);
+  }
+  std::array<float, 12> m;
+  std::memcpy(m.data(), c.m, sizeof c.m);
+  return m;
+}
+
+ImageRandomColorTwist::ImageRandomColorTwist(std::string ikey, const std::array<bool, 4>& has,
+                                             const std::array<Range, 4>& range, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), has_(has), range_(range) {
+  static const char* const names[4] = {"brightness", "contrast", "saturation", "hue"};
+  for (int k = 0; k < 4; k++) {
+    if (!has_[k]) continue;
+    const Range& r = range_[k];
+    if (!std::isfinite(r.first) || !std::isfinite(r.second))
+      throw std::invalid_argument(std::string("image_random_color_twist: ") + names[k] + " range must be finite");
+    if (r.first > r.second)
+      throw std::invalid_argument(std::string("image_random_color_twist: ") + names[k] + " range has lo > hi");
+    if (k < 3 && r.first < 0.0)
+      throw std::invalid_argument(std::string("image_random_color_twist: ") + names[k] + " must be >= 0");
+  }
+}
+
+std::array<float, 12> ImageRandomColorTwist::draw() const {
+  double f[4] = {1.0, 1.0, 1.0, 0.0};
+  auto st = get_state();
+  for (int k = 0; k < 4; k++)
+    if (has_[k]) f[k] = std::uniform_real_distribution<double>(range_[k].first, range_[k].second)(st->gen);
+  return color_twist(f[0], f[1], f[2], f[3]);
+}
+
+std::shared_ptr<Array> ImageRandomColorTwist::apply_image(const std::shared_ptr<Array>& img) const {
+  return plan_color(img, draw());
+}
+
+// one draw, the same matrix for every frame
+std::shared_ptr<Array> ImageRandomColorTwist::apply_video(const std::shared_ptr<Array>& video) const {
+  const std::array<float, 12> m = draw();
+  std::vector<std::shared_ptr<Array>> frames;
+  for (int64_t i = 0; i < video->shape(0); i++) frames.push_back(plan_color(video_frame(video, i), m));
+  if (frames.empty()) throw std::runtime_error("applyVideo: empty video");
+  return stack_frames(frames);
 }
 
 namespace {

@@ -91,6 +91,13 @@ struct ImagePlan {
   // shape (C, crop_h, crop_w).
   bool formatted = false;
   OutFormat out;
+  // image_color_twist / image_color_matrix / image_random_color_twist: the
+  // launch maps every result pixel through mxd_color `color` (row-major 3 x 4,
+  // offsets in byte units) before the output form above.  A pointwise map:
+  // crops and mirrors still compose on the plan; a resize or a second colour
+  // op materialises the first.
+  bool colored = false;
+  std::array<float, 12> color{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
   int64_t channels() const;
 };
 
@@ -310,6 +317,45 @@ class ImageNormalize : public ImageOp {
  private:
   std::vector<float> mean_, std_;
   OutFormat fmt_;
+};
+
+// Per-image colour transform (an addition to the reference's surface): a
+// 3 x 4 affine map of the RGB result bytes, rounded and clamped back to bytes
+// (DESIGN.md section 2), fused into the batch launch.  The op only marks the
+// pending plan.  RGB images only: "image_color_twist: image must have 3
+// channels" otherwise.  `matrix`: row-major 3 x 4, offsets in byte units.
+class ImageColorMatrix : public ImageOp {
+ public:
+  ImageColorMatrix(std::string ikey, const std::array<float, 12>& matrix, std::string okey);
+  std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+
+ private:
+  std::array<float, 12> m_;
+};
+
+// brightness, fixed-centre (0.5) contrast, saturation, hue (degrees):
+// mxd_color_twist_matrix's matrix.  Negative or non-finite factors throw
+// std::invalid_argument.
+std::array<float, 12> color_twist(double brightness, double contrast, double saturation, double hue);
+
+// Each factor drawn per image from its (lo, hi) range with one
+// std::uniform_real_distribution<double> draw from the thread's State
+// generator, in the order brightness, contrast, saturation, hue; a factor
+// without a range draws nothing and stays at its default.  A video draws once
+// for all its frames.
+class ImageRandomColorTwist : public ImageOp {
+ public:
+  using Range = std::pair<double, double>;
+  // has[k]: range[k] is given (k: brightness, contrast, saturation, hue)
+  ImageRandomColorTwist(std::string ikey, const std::array<bool, 4>& has, const std::array<Range, 4>& range,
+                        std::string okey);
+  std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+  std::shared_ptr<Array> apply_video(const std::shared_ptr<Array>& video) const override;
+
+ private:
+  std::array<float, 12> draw() const;
+  std::array<bool, 4> has_;
+  std::array<Range, 4> range_;
 };
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the

@@ -297,6 +297,40 @@ std::vector<float> channel_values(const py::object& v, const char* what) {
   throw std::invalid_argument(std::string("image_normalize: ") + what + " must be None, a number or a sequence of numbers");
 }
 
+// image_color_matrix's matrix: a 3 x 3 or 3 x 4 nested sequence or array, for
+// [r g b 1] in [0, 1] units -> row-major 3 x 4 with the offsets scaled to byte
+// units (x 255, in float32).
+std::array<float, 12> color_matrix(const py::object& v) {
+  std::vector<std::vector<float>> rows;
+  try {
+    rows = v.cast<std::vector<std::vector<float>>>();
+  } catch (const py::cast_error&) {
+    throw std::invalid_argument("image_color_matrix: matrix must be a 3x3 or 3x4 nested sequence or array of numbers");
+  }
+  if (rows.size() != 3 || (rows[0].size() != 3 && rows[0].size() != 4) || rows[1].size() != rows[0].size() ||
+      rows[2].size() != rows[0].size())
+    throw std::invalid_argument("image_color_matrix: matrix must be 3x3 or 3x4");
+  std::array<float, 12> m{};
+  for (int r = 0; r < 3; r++)
+    for (size_t k = 0; k < rows[r].size(); k++) {
+      if (!std::isfinite(rows[r][k])) throw std::invalid_argument("image_color_matrix: entries must be finite");
+      m[4 * r + k] = k == 3 ? rows[r][k] * 255.0f : rows[r][k];
+    }
+  return m;
+}
+
+// image_random_color_twist's arguments: None or a (lo, hi) pair each.
+void color_range(const py::object& v, const char* what, int k, std::array<bool, 4>& has,
+                 std::array<ImageRandomColorTwist::Range, 4>& range) {
+  has[k] = !v.is_none();
+  if (!has[k]) return;
+  try {
+    range[k] = v.cast<std::pair<double, double>>();
+  } catch (const py::cast_error&) {
+    throw std::invalid_argument(std::string("image_random_color_twist: ") + what + " must be None or a (lo, hi) pair");
+  }
+}
+
 // ------------------------------------------------------------ dataset ops
 // The ops every Dataset (Buffer and Stream) carries (wrap_dataset.h).
 template <class D, class Wrap>
@@ -392,7 +426,36 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
                                                                channel_values(std, "std"), dtype, layout, output_key));
           },
           py::arg("key"), py::arg("mean") = py::none(), py::arg("std") = py::none(), py::arg("dtype") = "float32",
-          py::arg("layout") = "hwc", py::arg("output_key") = "");
+          py::arg("layout") = "hwc", py::arg("output_key") = "")
+      .def(
+          "image_color_twist",
+          [wrap](const Self& self, const std::string& key, double brightness, double contrast, double saturation,
+                 double hue, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageColorMatrix>(
+                                  key, color_twist(brightness, contrast, saturation, hue), output_key));
+          },
+          py::arg("key"), py::arg("brightness") = 1.0, py::arg("contrast") = 1.0, py::arg("saturation") = 1.0,
+          py::arg("hue") = 0.0, py::arg("output_key") = "")
+      .def(
+          "image_color_matrix",
+          [wrap](const Self& self, const std::string& key, const py::object& matrix, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageColorMatrix>(key, color_matrix(matrix), output_key));
+          },
+          py::arg("key"), py::arg("matrix"), py::arg("output_key") = "")
+      .def(
+          "image_random_color_twist",
+          [wrap](const Self& self, const std::string& key, const py::object& brightness, const py::object& contrast,
+                 const py::object& saturation, const py::object& hue, const std::string& output_key) {
+            std::array<bool, 4> has{};
+            std::array<ImageRandomColorTwist::Range, 4> range{};
+            color_range(brightness, "brightness", 0, has, range);
+            color_range(contrast, "contrast", 1, has, range);
+            color_range(saturation, "saturation", 2, has, range);
+            color_range(hue, "hue", 3, has, range);
+            return wrap(self, std::make_shared<ImageRandomColorTwist>(key, has, range, output_key));
+          },
+          py::arg("key"), py::arg("brightness") = py::none(), py::arg("contrast") = py::none(),
+          py::arg("saturation") = py::none(), py::arg("hue") = py::none(), py::arg("output_key") = "");
 }
 
 using PadMap = std::unordered_map<std::string, double>;
@@ -625,6 +688,14 @@ PYBIND11_MODULE(_pipeline, m) {
       d["format"] = f;
     } else {
       d["format"] = py::none();
+    }
+    // the colour matrix as mxd_color holds it: three rows of four, offsets in byte units
+    if (p.colored) {
+      std::vector<std::vector<float>> rows;
+      for (int r = 0; r < 3; r++) rows.emplace_back(p.color.begin() + 4 * r, p.color.begin() + 4 * r + 4);
+      d["color"] = rows;
+    } else {
+      d["color"] = py::none();
     }
     return d;
   });

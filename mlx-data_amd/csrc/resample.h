@@ -184,6 +184,24 @@ struct FmtRowDev {
 };
 static_assert(sizeof(FmtRowDev) == 48, "FmtRowDev layout");
 int launch_format_rows(const FmtRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
+// u8 RGB rows -> colour-transformed rows in any output form (color_rows.hip):
+// the second pass of a colour call (mxd_color), whose every image is resized
+// into u8 scratch rows.  One entry per image: format_rows' fields and the
+// image's matrix (part of the uploaded bytes, so a cached descriptor slot
+// serves the same matrices only).  One workgroup per kColorRows rows of an
+// image, numbered through blk_begin.  fmt.table == nullptr: u8 output (HWC);
+// else the table's elements, as format_rows writes them.
+constexpr int kColorRows = 8;
+struct ColorRowDev {
+  const uint8_t* src;  // u8 rows: 16-byte aligned base, src_stride a multiple of 16
+  void* dst;
+  int64_t src_stride, dst_stride;
+  int32_t crop_w, crop_h, channels;
+  int32_t blk_begin;
+  float m[12];  // mxd_color::m, row-major
+};
+static_assert(sizeof(ColorRowDev) == 96, "ColorRowDev layout");
+int launch_color_rows(const ColorRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
 // Waves of this configuration the device runs at once (occupancy x CUs), 0 if unknown.
 int wave_capacity(const WaveCfg& cfg, int device);
 // Diagnostics: the occupancy API's blocks per CU, the kernel's VGPRs and LDS

@@ -42,6 +42,8 @@ EXPORTS = (
     "mxd_narrow_returns",
     "mxd_out_format_table", "mxd_resize_crop_batch_fmt", "mxd_resize_crop_to_device_fmt",
     "mxd_jpeg_resize_crop_to_device_fmt",
+    "mxd_color_twist_matrix", "mxd_color_apply_u8", "mxd_resize_crop_batch_color",
+    "mxd_resize_crop_to_device_color", "mxd_jpeg_resize_crop_to_device_color",
 )
 
 MXD_ELEM_F32 = 0
@@ -288,6 +290,58 @@ def resize_crop_to_device_fmt(images, n, fmt, device=0):
 
 def jpeg_resize_crop_to_device_fmt(images, n, fmt, device=0):
     check(lib().mxd_jpeg_resize_crop_to_device_fmt(images, n, ctypes.byref(fmt) if fmt is not None else None, device))
+
+
+class MxdColor(ctypes.Structure):
+    """struct mxd_color (include/mxd_amd.h): a 3 x 4 map of an RGB pixel's
+    result bytes, m[c][3] in byte units."""
+
+    _fields_ = [("m", (ctypes.c_float * 4) * 3)]
+
+
+def color_twist_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0):
+    """mxd_color_twist_matrix: the (3, 4) float32 matrix of a twist (hue in degrees)."""
+    c = MxdColor()
+    check(lib().mxd_color_twist_matrix(ctypes.c_double(brightness), ctypes.c_double(contrast),
+                                       ctypes.c_double(saturation), ctypes.c_double(hue), ctypes.byref(c)))
+    return np.ctypeslib.as_array(c.m).astype(np.float32).reshape(3, 4).copy()
+
+
+def make_colors(matrices):
+    """(3, 4) matrices in byte units (mxd_color::m) -> ctypes array of mxd_color."""
+    matrices = [np.asarray(m, np.float32).reshape(3, 4) for m in matrices]
+    arr = (MxdColor * max(1, len(matrices)))()
+    for i, m in enumerate(matrices):
+        for r in range(3):
+            for k in range(4):
+                arr[i].m[r][k] = float(m[r, k])
+    return arr
+
+
+def color_apply_u8(rgb, matrix):
+    """mxd_color_apply_u8: the CPU statement of the colour map on (..., 3) uint8 pixels."""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    out = np.empty_like(rgb)
+    check(lib().mxd_color_apply_u8(rgb.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(rgb.size // 3),
+                                   make_colors([matrix]), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def _fmt_ref(fmt):
+    return ctypes.byref(fmt) if fmt is not None else None
+
+
+def resize_crop_batch_color(images, colors, n, out_dtype=MXD_U8, fmt=None, device=0, stream=None):
+    check(lib().mxd_resize_crop_batch_color(images, colors, n, out_dtype, _fmt_ref(fmt), device,
+                                            ctypes.c_void_p(stream)))
+
+
+def resize_crop_to_device_color(images, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_resize_crop_to_device_color(images, colors, n, out_dtype, _fmt_ref(fmt), device))
+
+
+def jpeg_resize_crop_to_device_color(images, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_jpeg_resize_crop_to_device_color(images, colors, n, out_dtype, _fmt_ref(fmt), device))
 
 
 def set_kernel_policy(policy):

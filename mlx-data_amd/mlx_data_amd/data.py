@@ -60,6 +60,24 @@ A pending image carries the filter of its one resize (a second resize
 materialises the first); a resize to the size the image already has is the
 identity for every filter.
 
+Photometric augmentation stays in the launch too (the third addition):
+``image_color_twist(key, brightness=1.0, contrast=1.0, saturation=1.0,
+hue=0.0, output_key="")``, ``image_color_matrix(key, matrix, output_key="")``
+(a 3x3 or 3x4 matrix for ``[r g b 1]`` in [0, 1] units) and
+``image_random_color_twist(key, brightness=None, contrast=None,
+saturation=None, hue=None, output_key="")`` (each ``None`` or a ``(lo, hi)``
+range, drawn per image -- once per video -- from the ``set_state`` generator
+in that order), with their ``_if`` forms.  The map is a per-pixel 3x4 affine
+on the uint8 result, rounded and clamped back to uint8: brightness scales,
+contrast scales about 0.5 (the fixed-centre form, not torchvision's blend with
+the image mean), saturation blends with the luma, hue (degrees) rotates the
+YIQ chroma; hue is applied first and brightness last.  RGB images only.  The
+op only marks the pending image: crops and flips still compose after it,
+``image_to_float`` / ``image_normalize`` stack on top, and ``batch`` runs the
+map as one more kernel behind the resize of the same call.  A resize or a
+second colour op after it materialises the first.  Bad arguments raise
+``ValueError`` when the op is made.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole
@@ -118,7 +136,8 @@ def _add_if_variants(cls):
     unchanged (``Dataset::*_if``, ``Dataset.cpp``)."""
     for name in ("key_transform", "load_image", "image_resize_smallest_side", "image_resize",
                  "image_center_crop", "image_random_crop", "image_random_h_flip", "image_random_area_crop",
-                 "image_rotate", "image_channel_reduction", "image_to_float", "image_normalize"):
+                 "image_rotate", "image_channel_reduction", "image_to_float", "image_normalize",
+                 "image_color_twist", "image_color_matrix", "image_random_color_twist"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 
