@@ -58,10 +58,15 @@ extern "C" {
  * 7, added without a new number (test for MXD_HAS_COLOR / the symbols): the
  * per-image colour transform -- mxd_color, mxd_color_twist_matrix,
  * mxd_color_apply_u8, mxd_resize_crop_batch_color,
- * mxd_resize_crop_to_device_color, mxd_jpeg_resize_crop_to_device_color. */
+ * mxd_resize_crop_to_device_color, mxd_jpeg_resize_crop_to_device_color.
+ * 7, added without a new number (test for MXD_HAS_TONE / the symbols): the
+ * per-image tone operations -- mxd_tone_op, mxd_tone, mxd_tone_table_u8,
+ * mxd_tone_apply_u8, mxd_resize_crop_batch_tone,
+ * mxd_resize_crop_to_device_tone, mxd_jpeg_resize_crop_to_device_tone. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
+#define MXD_HAS_TONE 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -556,6 +561,77 @@ int mxd_resize_crop_to_device_color(const mxd_image* images, const mxd_color* co
                                     const mxd_out_format* fmt, int32_t device);
 int mxd_jpeg_resize_crop_to_device_color(const mxd_jpeg_image* images, const mxd_color* colors, int32_t n,
                                          int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
+
+/* ---- per-image tone operations (ABI 7 additions; feature test: MXD_HAS_TONE)
+ *
+ * A tone operation replaces every result byte q_c (c = 0..2) of an RGB image's
+ * crop window -- exactly what MXD_U8 gives -- with t[c][q_c], a 3 x 256 byte
+ * table built from the operation's parameters and, for the last three, from
+ * statistics of that window: N its pixel count, H_c[v] the number of pixels
+ * whose channel c equals v, H_L[v] the same over the luma byte
+ * L = (19595 q0 + 38470 q1 + 7471 q2 + 32768) >> 16.  Mirrors do not change
+ * the statistics, crops do.  The arithmetic is Pillow's (ImageOps.posterize,
+ * solarize, autocontrast, equalize; ImageEnhance.Contrast), bit for bit: it
+ * truncates where the rest of this library rounds.
+ *
+ *   POSTERIZE     arg = bits, 1..8: t = v & ((0xff << (8 - bits)) & 0xff)
+ *   SOLARIZE      arg = threshold, 0..256: t = v < threshold ? v : 255 - v
+ *   AUTOCONTRAST  per channel, lo / hi the smallest / largest v with
+ *                 H_c[v] > 0; identity if hi <= lo, else in double, each
+ *                 operation rounded, none fused: scale = 255.0 / (hi - lo),
+ *                 offset = -lo * scale, t = clamp(trunc(v * scale + offset), 0, 255)
+ *   EQUALIZE      per channel, integers: last = H_c at the largest non-empty
+ *                 bin; identity if at most one bin is non-empty or
+ *                 step = (N - last) / 255 is 0, else
+ *                 t = min(255, (step / 2 + sum_{u < v} H_c[u]) / step)
+ *   CONTRAST      factor f, finite, 0 <= f <= 1e6: one table for all channels;
+ *                 m = (int)((double)(sum_v v H_L[v]) / (double)N + 0.5); in
+ *                 float32, each operation rounded, none fused:
+ *                 x = (float)m + f * (float)(v - m); t = (uint8) trunc(x) for
+ *                 0 <= f <= 1, else 0 for x <= 0, 255 for x >= 255, trunc(x)
+ *                 between: the blend with the grey of the image's mean luma.
+ *
+ * The colour matrix of the same call, if any, reads the new bytes, and the
+ * output form reads the matrix's result. */
+enum mxd_tone_op {
+  MXD_TONE_NONE = 0,
+  MXD_TONE_POSTERIZE = 1,
+  MXD_TONE_SOLARIZE = 2,
+  MXD_TONE_AUTOCONTRAST = 3,
+  MXD_TONE_EQUALIZE = 4,
+  MXD_TONE_CONTRAST = 5
+};
+
+typedef struct mxd_tone {
+  int32_t op;       /* mxd_tone_op */
+  int32_t arg;      /* POSTERIZE: bits; SOLARIZE: threshold; else not read */
+  float factor;     /* CONTRAST: f; else not read */
+  int32_t reserved; /* must be 0 */
+} mxd_tone;
+
+/* Host only: the CPU statement of the arithmetic above.  The table of `tone`
+ * for the npixels packed RGB pixels at rgb (table[256 c + v] = t[c][v]), and
+ * the pixels looked up in it (out may equal rgb).  MXD_ERR_INVALID for a bad
+ * tone (as the calls below). */
+int mxd_tone_table_u8(const uint8_t* rgb, int64_t npixels, const mxd_tone* tone, uint8_t table[768]);
+int mxd_tone_apply_u8(const uint8_t* rgb, int64_t npixels, const mxd_tone* tone, uint8_t* out);
+
+/* The _color calls with tones[i] applied to images[i]'s result before
+ * colors[i].  colors may be NULL: no matrix.  fmt and out_dtype mean what they
+ * mean there, with every check of theirs.  Device destinations only.
+ * MXD_ERR_INVALID (the message names the image and the field) for a null
+ * tones, an unknown op, bits outside 1..8, a threshold outside 0..256, a
+ * negative, non-finite or too large factor, a non-zero reserved, or
+ * channels != 3; everything is validated before any launch.  Every image is
+ * resized as a u8 image into a scratch by the kernels of the plain calls;
+ * three more launches on the same stream build the histograms, the tables and
+ * the destinations. */
+int mxd_resize_crop_batch_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
+                               int32_t out_dtype, const mxd_out_format* fmt, int32_t device, void* stream);
+int mxd_resize_crop_to_device_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
+                                   int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
+int mxd_jpeg_resize_crop_to_device_tone(const mxd_jpeg_image* images, const mxd_tone* tones, const mxd_color* colors,
+                                        int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
 
 /* Diagnostics: where a host-side pipeline's time goes, summed over every
  * thread since the last reset (reset != 0 zeroes them after reading).

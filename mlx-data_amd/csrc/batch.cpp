@@ -407,13 +407,13 @@ int launch_all(const BatchLayout& L, const ImgDev* dev, Workspace* ws, const mxd
 
 // One launchable batch: its layout, the upload, the launches.
 int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-                   const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors) {
+                   const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones) {
   DeviceGuard guard(device);
   BatchLayout L;
-  if (int rc = build_layout(device_env(), device, images, n, stored, out_dtype, fmt, &L, colors)) return rc;
+  if (int rc = build_layout(device_env(), device, images, n, stored, out_dtype, fmt, &L, colors, tones)) return rc;
   mxd::OutFmtDev ofd{};
   std::unique_lock<std::mutex> scratch_hold;
-  if (fmt || colors)
+  if (fmt || colors || tones)
     if (int rc = take_scratch(L, fmt, device, stream, &ofd, &scratch_hold)) return rc;
   ImgDev* dev = nullptr;
   std::unique_lock<std::mutex> hold;
@@ -421,10 +421,18 @@ int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_
   bool hit = false;
   if (int rc = upload_descs(L.descs, device, stream, &dev, &hold, &ws, &hit)) return rc;
   // (a colour call's resize kernels run in their u8 mode: the format is color_rows')
-  int launch_rc = launch_all(L, dev, ws, fmt && !colors ? &ofd : nullptr, stream);
+  int launch_rc = launch_all(L, dev, ws, fmt && !colors && !tones ? &ofd : nullptr, stream);
   // The second pass of a formatted call, behind the joins: every resize
   // kernel that wrote scratch rows is ordered before it on the caller's stream.
-  if (launch_rc == MXD_OK && colors) {
+  if (launch_rc == MXD_OK && tones) {
+    // this call's statistics start from zero, whatever the stream's last call left
+    if (L.tone_stat_bytes > 0 &&
+        hipMemsetAsync(L.tone_ws, 0, L.tone_stat_bytes, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+      launch_rc = fail(MXD_ERR_DEVICE, std::string("tone workspace memset failed: ") + hipGetErrorString(hipGetLastError()));
+    else if (mxd::launch_tone(reinterpret_cast<const mxd::ToneRowDev*>(dev + L.fmt_at), L.fmt_count, L.tone_hist_blocks,
+                              L.fmt_blocks, ofd, L.tone_ws, L.tone_matrix, stream))
+      launch_rc = fail(MXD_ERR_DEVICE, std::string("tone launch failed: ") + hipGetErrorString(hipGetLastError()));
+  } else if (launch_rc == MXD_OK && colors) {
     if (mxd::launch_color_rows(reinterpret_cast<const mxd::ColorRowDev*>(dev + L.fmt_at), L.fmt_count, L.fmt_blocks, ofd,
                                stream))
       launch_rc = fail(MXD_ERR_DEVICE, std::string("color_rows launch failed: ") + hipGetErrorString(hipGetLastError()));
@@ -454,19 +462,21 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 }
 
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors) {
+              const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones) {
   mxd_out_format f32_fmt;
-  if (colors)
+  if (tones) {
+    if (int rc = tone_prepare(images, tones, colors, n, &out_dtype, &fmt, &f32_fmt)) return rc;
+  } else if (colors)
     if (int rc = color_prepare(images, colors, n, &out_dtype, &fmt, &f32_fmt)) return rc;
   if (int rc = validate_batch(images, n, &out_dtype, device, fmt)) return rc;
   if (n == 0) return MXD_OK;
-  // (a colour call's images all have three channels: one launchable batch,
-  // so colors[i] stays beside images[i])
-  const std::vector<SubBatch> subs = colors ? std::vector<SubBatch>{} : split_batch(images, n, stored);
-  if (subs.empty()) return run_launchable(images, n, out_dtype, device, stream, stored, fmt, colors);
+  // (a colour or tone call's images all have three channels: one launchable
+  // batch, so colors[i] and tones[i] stay beside images[i])
+  const std::vector<SubBatch> subs = colors || tones ? std::vector<SubBatch>{} : split_batch(images, n, stored);
+  if (subs.empty()) return run_launchable(images, n, out_dtype, device, stream, stored, fmt, colors, tones);
   for (const SubBatch& s : subs)
     if (int rc = run_launchable(s.images.data(), (int32_t)s.images.size(), out_dtype, device, stream,
-                                stored ? s.stored.data() : nullptr, fmt, nullptr))
+                                stored ? s.stored.data() : nullptr, fmt, nullptr, nullptr))
       return rc;
   return MXD_OK;
 }

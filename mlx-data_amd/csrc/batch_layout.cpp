@@ -349,7 +349,7 @@ void place_colored(Batch& b) {
 // the band launches whose images differ in unit count (int32 each), then
 // format_rows' entries: part of the upload's bytes, so a cached slot is
 // reused only with the same scratch rows and destinations.
-void append_tables(Batch& b, const mxd_image* callers, const mxd_color* colors) {
+void append_tables(Batch& b, const mxd_image* callers, const mxd_color* colors, const mxd_tone* tones) {
   BatchLayout& L = b.L;
   std::vector<int32_t> unit_tables;
   for (BatchLayout::BandGroup& g : L.bands) {
@@ -366,6 +366,42 @@ void append_tables(Batch& b, const mxd_image* callers, const mxd_color* colors) 
   if (!unit_tables.empty())
     std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.tables_at), unit_tables.data(), unit_tables.size() * 4);
   L.fmt_at = L.descs.size();
+  if (tones) {
+    // tone_rows' entries, in batch order: ops, parameters and matrices are
+    // part of the upload's bytes, so a cached slot is reused only for the
+    // same ones.  The workspace follows the scratch rows: statistics first.
+    std::vector<mxd::ToneRowDev> rows(b.n);
+    int32_t stats = 0;
+    for (int32_t i = 0; i < b.n; i++) {
+      const mxd_image& im = L.images[i];
+      mxd::ToneRowDev& r = rows[i];
+      r = mxd::ToneRowDev{};
+      r.src = static_cast<const uint8_t*>(im.dst), r.dst = callers[i].dst;
+      r.src_stride = im.dst_stride, r.dst_stride = callers[i].dst_stride;
+      r.crop_w = im.crop_w, r.crop_h = im.crop_h, r.channels = im.channels;
+      r.blk_begin = L.fmt_blocks;
+      for (int k = 0; k < 12; k++) r.m[k] = colors ? color_entry(colors[i].m[k / 4][k % 4]) : k % 5 == 0 ? 1.0f : 0.0f;
+      r.op = tones[i].op, r.arg = tones[i].arg, r.factor = tones[i].factor;
+      r.hist_begin = L.tone_hist_blocks;
+      r.stat_off = -1;
+      if (mxd::tone_needs_stats(r.op)) {
+        r.stat_off = stats * (int32_t)(mxd::kToneStatWords * sizeof(uint32_t));
+        stats++;
+        L.tone_hist_blocks += (im.crop_h + mxd::kToneHistRows - 1) / mxd::kToneHistRows;
+      }
+      L.fmt_blocks += (im.crop_h + mxd::kColorRows - 1) / mxd::kColorRows;
+    }
+    L.tone_stat_bytes = (size_t)stats * mxd::kToneStatWords * sizeof(uint32_t);
+    for (int32_t i = 0; i < b.n; i++) rows[i].lut_off = (int32_t)(L.tone_stat_bytes + (size_t)i * mxd::kToneLutBytes);
+    L.tone_matrix = colors != nullptr;
+    L.tone_ws_at = (L.scratch_bytes + 255) & ~(size_t)255;
+    L.scratch_bytes = L.tone_ws_at + L.tone_stat_bytes + (size_t)b.n * mxd::kToneLutBytes;
+    L.fmt_count = b.n;
+    const size_t bytes = rows.size() * sizeof(mxd::ToneRowDev);
+    L.descs.resize(L.fmt_at + (bytes + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+    std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.fmt_at), rows.data(), bytes);
+    return;
+  }
   if (colors) {
     // color_rows' entries, in batch order: the matrices are part of the
     // upload's bytes, so a cached slot is reused only for the same matrices.
@@ -408,7 +444,12 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity) {
 
 void BatchLayout::add_scratch(uint8_t* base) {
   for (int32_t k = 0; k < n; k++)
-    if (colored || !plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
+    if (colored || toned || !plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
+  if (toned) {
+    for (int32_t j = 0; j < fmt_count; j++) tone_rows()[j].src = base + reinterpret_cast<uintptr_t>(tone_rows()[j].src);
+    tone_ws = base + tone_ws_at;
+    return;
+  }
   if (colored) {
     for (int32_t j = 0; j < fmt_count; j++)
       color_rows()[j].src = base + reinterpret_cast<uintptr_t>(color_rows()[j].src);
@@ -418,11 +459,13 @@ void BatchLayout::add_scratch(uint8_t* base) {
 }
 
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
-                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors) {
+                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors,
+                 const mxd_tone* tones) {
   *out = BatchLayout{};
   BatchLayout& L = *out;
   L.n = n;
-  L.colored = colors != nullptr;
+  L.toned = tones != nullptr;
+  L.colored = colors != nullptr && !tones;
   // A formatted call plans its kernels as a u8 call does: the wave kernels
   // exist in the same shapes in every output mode and write any element
   // alignment, and an image they do not take is resized into u8 scratch rows
@@ -430,7 +473,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   const mxd_image* const callers = images;
   // A colour call plans every image so, and keeps every u8 kernel a plain u8
   // call has (the cubic filters' and JPEG plane sources' wave kernels too).
-  if (fmt || colors) {
+  if (fmt || colors || tones) {
     out_dtype = MXD_U8;
     L.images.assign(images, images + n);
     for (mxd_image& im : L.images) {
@@ -439,9 +482,9 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
     }
     images = L.images.data();
   }
-  Batch b{env, device, images, stored, n, images[0].channels, out_dtype, fmt != nullptr && !colors, L, {}};
+  Batch b{env, device, images, stored, n, images[0].channels, out_dtype, fmt != nullptr && !colors && !tones, L, {}};
   if (int rc = plan_images(b)) return rc;
-  if (colors) place_colored(b);
+  if (colors || tones) place_colored(b);
   else if (fmt) place_formatted(b, callers);
   // Descriptors of one upload: band-kernel images first, then wave-kernel
   // images, then the general kernel's.
@@ -450,7 +493,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = band_groups(b)) return rc;
   if (int rc = wave_groups(b)) return rc;
   if (int rc = general_group(b)) return rc;
-  append_tables(b, callers, colors);
+  append_tables(b, callers, colors, tones);
   // Largest first (a band unit is a workgroup, ~4 wave units).
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});

@@ -259,6 +259,15 @@ int mxd_resize_crop_batch_color(const mxd_image* images, const mxd_color* colors
   return run_batch(images, n, out_dtype, device, stream, nullptr, fmt, colors);
 }
 
+int mxd_resize_crop_batch_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
+                               int32_t out_dtype, const mxd_out_format* fmt, int32_t device, void* stream) {
+  if (fmt)
+    if (int rc = fmt_validate(fmt, 0)) return rc;
+  if (n > 0 && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
+  if (n <= 0) return run_batch(images, n, fmt ? MXD_U8 : out_dtype, device, stream, nullptr, fmt);
+  return run_batch(images, n, out_dtype, device, stream, nullptr, fmt, colors, tones);
+}
+
 int mxd_set_kernel_policy(int32_t policy) { return g_policy.exchange(policy); }
 
 int mxd_set_tuning(int32_t knob, int32_t value) {
@@ -457,6 +466,14 @@ int mxd_resize_crop_to_device_color(const mxd_image* images, const mxd_color* co
   return host_path(images, n, out_dtype, device, true, nullptr, fmt, n > 0 ? colors : nullptr);
 }
 
+int mxd_resize_crop_to_device_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
+                                   int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
+  if (fmt)
+    if (int rc = fmt_validate(fmt, 0)) return rc;
+  if (n > 0 && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
+  return host_path(images, n, out_dtype, device, true, nullptr, fmt, n > 0 ? colors : nullptr, n > 0 ? tones : nullptr);
+}
+
 int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device) {
   if (int rc = fmt_validate(fmt, 0)) return rc;
   return host_path(images, n, MXD_U8, device, true, nullptr, fmt);
@@ -559,6 +576,14 @@ int mxd_jpeg_resize_crop_to_device_color(const mxd_jpeg_image* images, const mxd
     if (int rc = fmt_validate(fmt, 0)) return rc;
   if (n > 0 && !colors) return fail(MXD_ERR_INVALID, "mxd: null colors");
   return jpeg_path(images, n, out_dtype, device, true, fmt, n > 0 ? colors : nullptr);
+}
+
+int mxd_jpeg_resize_crop_to_device_tone(const mxd_jpeg_image* images, const mxd_tone* tones, const mxd_color* colors,
+                                        int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
+  if (fmt)
+    if (int rc = fmt_validate(fmt, 0)) return rc;
+  if (n > 0 && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
+  return jpeg_path(images, n, out_dtype, device, true, fmt, n > 0 ? colors : nullptr, n > 0 ? tones : nullptr);
 }
 
 int mxd_jpeg_resize_crop_to_device_fmt(const mxd_jpeg_image* images, int32_t n, const mxd_out_format* fmt,

@@ -302,6 +302,18 @@ struct BatchLayout {
   // format_rows' place from fmt_at (fmt_count of them, fmt_blocks workgroups).
   bool colored = false;
   mxd::ColorRowDev* color_rows() { return reinterpret_cast<mxd::ColorRowDev*>(descs.data() + fmt_at); }
+  // Tone call: a colour call's layout with tone_rows' entries (the image's
+  // matrix, or the identity, and its mxd_tone) in color_rows' place.  Behind
+  // the scratch rows, from tone_ws_at (a multiple of 256; counted in
+  // scratch_bytes), lies the call's workspace: tone_stat_bytes of statistics
+  // (one block per image whose op needs them; zeroed for every call), then one
+  // table per image.  tone_hist_blocks: tone_hist's workgroups.  tone_ws: the
+  // workspace's address once add_scratch() knows the scratch.
+  bool toned = false, tone_matrix = false;
+  size_t tone_ws_at = 0, tone_stat_bytes = 0;
+  int32_t tone_hist_blocks = 0;
+  uint8_t* tone_ws = nullptr;
+  mxd::ToneRowDev* tone_rows() { return reinterpret_cast<mxd::ToneRowDev*>(descs.data() + fmt_at); }
   const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
   void add_scratch(uint8_t* base);
 };
@@ -309,8 +321,11 @@ struct BatchLayout {
 // are launch arguments, not part of the layout).  colors != nullptr: a colour
 // call (colors[i] belongs to images[i]; planned as a u8 call into scratch
 // whatever fmt and out_dtype say: the output form is color_rows' alone).
+// tones != nullptr: a tone call (tones[i] belongs to images[i]; colors may be
+// null then: no matrix); planned like a colour call.
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
-                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors = nullptr);
+                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors = nullptr,
+                 const mxd_tone* tones = nullptr);
 
 // The images of a batch for which pred holds, in batch order, with their
 // stored entries.
@@ -344,7 +359,8 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 // (MXD_U8 / MXD_F32_DIV255).  Every image is resized into the scratch in u8
 // and one color_rows launch writes the destinations.
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored = nullptr, const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr);
+              const Stored* stored = nullptr, const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr,
+              const mxd_tone* tones = nullptr);
 
 // ---------------------------------------------------------------------------
 // Colour transform (color.cpp).
@@ -357,6 +373,17 @@ int color_validate(const mxd_image* images, const mxd_color* colors, int32_t n);
 // null stays null for MXD_U8) and *out_dtype the form the kernels are planned in.
 int color_prepare(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t* out_dtype,
                   const mxd_out_format** fmt, mxd_out_format* f32_fmt);
+
+// ---------------------------------------------------------------------------
+// Tone operations (tone.cpp).  run_batch's tones != nullptr: a tone call;
+// every image is resized into the scratch in u8, then tone_hist, tone_lut and
+// tone_rows run on the call's stream (colors may be null: no matrix).
+// tones[i] against images[i] (images may be null: the tones alone).
+int tone_validate(const mxd_image* images, const mxd_tone* tones, int32_t n);
+// The head of every tone call: color_prepare with the tones' validation (and
+// the colours' when there are any).
+int tone_prepare(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t* out_dtype,
+                 const mxd_out_format** fmt, mxd_out_format* f32_fmt);
 
 // ---------------------------------------------------------------------------
 // Formatted outputs (outfmt.cpp).
@@ -378,9 +405,9 @@ int fmt_device_table(int32_t device, const mxd_out_format& fmt, int32_t channels
 // colour call with the chunk's slice of the matrices.
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
               const mxd_jpeg_image* jpeg = nullptr, const mxd_out_format* fmt = nullptr,
-              const mxd_color* colors = nullptr);
+              const mxd_color* colors = nullptr, const mxd_tone* tones = nullptr);
 int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr);
+              const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr, const mxd_tone* tones = nullptr);
 // mxd_host_stats counters: host-path calls, images, wall ns, device-wait ns,
 // coefficient parses, parse ns
 extern std::atomic<int64_t> g_host_stats[6];

@@ -120,6 +120,8 @@ struct HostCall {
   // not null: a colour call; colors[i] belongs to images[i], and a chunk's
   // launch gets the slice of its range
   const mxd_color* colors = nullptr;
+  // not null: a tone call (colors may be null then); sliced like colors
+  const mxd_tone* tones = nullptr;
   std::vector<Stage> st;
   std::vector<ChunkRange> chunks;
   HostCtx* ctx = nullptr;

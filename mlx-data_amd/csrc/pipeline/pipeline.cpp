@@ -262,22 +262,43 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
   std::vector<mxd_jpeg_image> jp;
   std::vector<std::shared_ptr<const JpegSource>> keep;  // alive for the call
   std::vector<mxd_color> pc, jc;  // the colours of `plain` and `jp`, image for image
-  bool colored = false;
+  std::vector<mxd_tone> pt, jt;   // and their tones
+  bool colored = false, toned = false;
   for (size_t i = 0; i < n; i++) {
     const Job& j = jobs[i];
     mxd_color c;
     std::memcpy(c.m, j.plan.color.data(), sizeof c.m);
     colored = colored || j.plan.colored;
+    mxd_tone t{};  // (MXD_TONE_NONE for a plan without a tone op)
+    if (j.plan.toned) t.op = j.plan.tone_op, t.arg = j.plan.tone_arg, t.factor = j.plan.tone_factor;
+    toned = toned || j.plan.toned;
     if (auto src = j.plan.src->jpeg()) {
       jp.push_back(jpeg_desc(j.plan, *src, j.dst, j.stride));
       jc.push_back(c);
+      jt.push_back(t);
       keep.push_back(std::move(src));
     } else {
       plain.push_back(plan_desc(j.plan, j.dst, j.stride));
       pc.push_back(c);
+      pt.push_back(t);
     }
   }
   g_run_jpeg.fetch_add((int64_t)jp.size());
+  // Some plan is toned: the whole launch goes through the _tone calls, plans
+  // without a tone op with MXD_TONE_NONE; no matrices unless some plan is
+  // coloured (then the others get the identity).  Device destinations only.
+  if (toned) {
+    if (!dst_device) throw std::logic_error("mxd: a tone launch needs device destinations");
+    mxd_out_format of{};
+    if (fmt) of = abi_format(*fmt, jobs[0]);
+    if (!jp.empty())
+      if (int rc = mxd_jpeg_resize_crop_to_device_tone(jp.data(), jt.data(), colored ? jc.data() : nullptr,
+                                                       (int32_t)jp.size(), dtype, fmt ? &of : nullptr, device))
+        return rc;
+    if (plain.empty()) return MXD_OK;
+    return mxd_resize_crop_to_device_tone(plain.data(), pt.data(), colored ? pc.data() : nullptr, (int32_t)plain.size(),
+                                          dtype, fmt ? &of : nullptr, device);
+  }
   // Some plan is coloured: the whole launch goes through the _color calls,
   // plans without a colour with the identity (exact).  Device destinations only.
   if (colored) {
@@ -470,8 +491,8 @@ void run_host(const std::vector<Job>& jobs, int32_t dtype, const OutFormat* fmt 
   const std::vector<Slice> sl = split_batch((int64_t)n, (int64_t)devs.size(), g_rr.fetch_add(k));
   // a coloured plan anywhere: every slice takes the device call and one copy
   // back, like a formatted batch (each slice carries its own jobs' matrices)
-  bool colored = false;
-  for (const Job& j : jobs) colored = colored || j.plan.colored;
+  bool colored = false;  // (or toned: device calls only, too)
+  for (const Job& j : jobs) colored = colored || j.plan.colored || j.plan.toned;
   auto slice = [&jobs, dtype, &devs, &sl, fmt, colored](size_t s) -> std::string {
     const Job* first = jobs.data() + sl[s].begin;
     const size_t count = (size_t)(sl[s].end - sl[s].begin);
@@ -670,7 +691,8 @@ std::shared_ptr<Array> plan_resize(const std::shared_ptr<Array>& img, int64_t dw
   // (an alpha-weighted same-size resize is not the identity: it zeroes the
   // colour of transparent pixels, so it runs before the next one)
   const bool identity_so_far =
-      p.resize_w == p.sw && p.resize_h == p.sh && !p.flip && !(p.resampled && p.channels() == 4) && !p.colored;
+      p.resize_w == p.sw && p.resize_h == p.sh && !p.flip && !(p.resampled && p.channels() == 4) && !p.colored &&
+      !p.toned;
   if (identity_so_far) {
     // crop-then-resize: the crop becomes the source window.
     p.sx += p.crop_x;
@@ -710,6 +732,11 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
     return out;
   }
   ImagePlan p = view(img);
+  if (p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) {
+    // the op's statistics are those of the window it saw: run it, crop its bytes
+    img->data();
+    p = view(img);
+  }
   p.crop_x = p.flip ? p.crop_x + p.crop_w - x - w : p.crop_x + x;
   p.crop_y += y;
   p.crop_w = w;
@@ -985,6 +1012,38 @@ std::shared_ptr<Array> ImageRandomColorTwist::apply_video(const std::shared_ptr<
   for (int64_t i = 0; i < video->shape(0); i++) frames.push_back(plan_color(video_frame(video, i), m));
   if (frames.empty()) throw std::runtime_error("applyVideo: empty video");
   return stack_frames(frames);
+}
+
+// ---- tone ops: mark the plan ---------------------------------------------------
+const char* tone_name(int32_t op) {
+  static const char* const names[] = {"none", "posterize", "solarize", "autocontrast", "equalize", "contrast"};
+  return op >= 0 && op <= MXD_TONE_CONTRAST ? names[op] : "none";
+}
+
+ImageTone::ImageTone(std::string ikey, int32_t op, int64_t arg, double factor, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), op_(op), arg_((int32_t)arg), factor_((float)factor) {
+  if (op_ == MXD_TONE_POSTERIZE && (arg < 1 || arg > 8))
+    throw std::invalid_argument("image_posterize: bits must be in 1..8");
+  if (op_ == MXD_TONE_SOLARIZE && (arg < 0 || arg > 256))
+    throw std::invalid_argument("image_solarize: threshold must be in 0..256");
+  if (op_ == MXD_TONE_CONTRAST && !(std::isfinite(factor) && factor >= 0.0 && factor <= 1e6))
+    throw std::invalid_argument("image_contrast: factor must be finite and in 0..1e6");
+}
+
+std::shared_ptr<Array> ImageTone::apply_image(const std::shared_ptr<Array>& img) const {
+  if (img->shape(2) != 3)
+    throw std::runtime_error(std::string("image_") + tone_name(op_) + ": image must have 3 channels, not " +
+                             std::to_string(img->shape(2)));
+  ImagePlan p = view(img);
+  if (p.toned || p.colored) {
+    // each op rounds to bytes and the launch runs tone before colour: run
+    // what is pending, look its bytes up
+    img->data();
+    p = view(img);
+  }
+  p.toned = true;
+  p.tone_op = op_, p.tone_arg = arg_, p.tone_factor = factor_;
+  return make(p);
 }
 
 namespace {

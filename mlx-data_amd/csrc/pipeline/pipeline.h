@@ -98,6 +98,17 @@ struct ImagePlan {
   // op materialises the first.
   bool colored = false;
   std::array<float, 12> color{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
+  // image_posterize / _solarize / _autocontrast / _equalize / _contrast: the
+  // launch looks every result byte up in the table of mxd_tone {tone_op,
+  // tone_arg, tone_factor} before the colour map and the output form above.
+  // Mirrors compose after every tone op; crops after the pointwise ones
+  // (posterize, solarize) only: the others' statistics are those of the
+  // window the op saw, so a crop materialises them first, as a resize or a
+  // second tone op (or a tone op on a coloured plan: tone runs before colour)
+  // materialises any.
+  bool toned = false;
+  int32_t tone_op = 0, tone_arg = 0;
+  float tone_factor = 0.0f;
   int64_t channels() const;
 };
 
@@ -357,6 +368,25 @@ class ImageRandomColorTwist : public ImageOp {
   std::array<bool, 4> has_;
   std::array<Range, 4> range_;
 };
+
+// Per-image tone operations (an addition to the reference's surface):
+// Pillow's posterize, solarize, autocontrast, equalize and mean-grey contrast
+// of the RGB result bytes, bit for bit, fused into the
+// batch launch.  The op only marks the pending plan.  RGB images only:
+// "image_equalize: image must have 3 channels, not N" otherwise.  Bad
+// arguments throw std::invalid_argument from the constructor.
+class ImageTone : public ImageOp {
+ public:
+  // op: mxd_tone_op; arg: posterize's bits / solarize's threshold; factor: contrast's
+  ImageTone(std::string ikey, int32_t op, int64_t arg, double factor, std::string okey);
+  std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+
+ private:
+  int32_t op_, arg_;
+  float factor_;
+};
+// "posterize", ... of an mxd_tone_op (the op is image_<name>).
+const char* tone_name(int32_t op);
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the
 // centre (core::image::rotate -> affine), one GPU pixel-map launch.

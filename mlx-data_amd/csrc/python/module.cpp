@@ -455,7 +455,37 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
             return wrap(self, std::make_shared<ImageRandomColorTwist>(key, has, range, output_key));
           },
           py::arg("key"), py::arg("brightness") = py::none(), py::arg("contrast") = py::none(),
-          py::arg("saturation") = py::none(), py::arg("hue") = py::none(), py::arg("output_key") = "");
+          py::arg("saturation") = py::none(), py::arg("hue") = py::none(), py::arg("output_key") = "")
+      .def(
+          "image_posterize",
+          [wrap](const Self& self, const std::string& key, int64_t bits, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageTone>(key, MXD_TONE_POSTERIZE, bits, 0.0, output_key));
+          },
+          py::arg("key"), py::arg("bits"), py::arg("output_key") = "")
+      .def(
+          "image_solarize",
+          [wrap](const Self& self, const std::string& key, int64_t threshold, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageTone>(key, MXD_TONE_SOLARIZE, threshold, 0.0, output_key));
+          },
+          py::arg("key"), py::arg("threshold") = 128, py::arg("output_key") = "")
+      .def(
+          "image_autocontrast",
+          [wrap](const Self& self, const std::string& key, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageTone>(key, MXD_TONE_AUTOCONTRAST, 0, 0.0, output_key));
+          },
+          py::arg("key"), py::arg("output_key") = "")
+      .def(
+          "image_equalize",
+          [wrap](const Self& self, const std::string& key, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageTone>(key, MXD_TONE_EQUALIZE, 0, 0.0, output_key));
+          },
+          py::arg("key"), py::arg("output_key") = "")
+      .def(
+          "image_contrast",
+          [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageTone>(key, MXD_TONE_CONTRAST, 0, factor, output_key));
+          },
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "");
 }
 
 using PadMap = std::unordered_map<std::string, double>;
@@ -696,6 +726,15 @@ PYBIND11_MODULE(_pipeline, m) {
       d["color"] = rows;
     } else {
       d["color"] = py::none();
+    }
+    // the tone op: (name, bits / threshold / factor; None for the parameterless ones)
+    if (p.toned) {
+      py::object arg = py::none();
+      if (p.tone_op == MXD_TONE_POSTERIZE || p.tone_op == MXD_TONE_SOLARIZE) arg = py::int_(p.tone_arg);
+      else if (p.tone_op == MXD_TONE_CONTRAST) arg = py::float_(p.tone_factor);
+      d["tone"] = py::make_tuple(tone_name(p.tone_op), arg);
+    } else {
+      d["tone"] = py::none();
     }
     return d;
   });

@@ -202,6 +202,45 @@ struct ColorRowDev {
 };
 static_assert(sizeof(ColorRowDev) == 96, "ColorRowDev layout");
 int launch_color_rows(const ColorRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
+// u8 RGB rows -> per-image byte tables -> (colour matrix) -> any output form
+// (tone_rows.hip): the second pass of a tone call (mxd_tone), whose every
+// image is resized into u8 scratch rows like a colour call's.  Three launches
+// on the call's stream: tone_hist adds the histograms of the images whose op
+// needs statistics into the workspace (one workgroup per kToneHistRows rows,
+// numbered through hist_begin; none for the other images), tone_lut turns
+// every image's statistics and parameters into its 3 x 256 byte table (one
+// workgroup per image), tone_rows looks every byte up, applies the matrix and
+// writes the destinations (color_rows' structure, numbered through
+// blk_begin).  One entry per image: color_rows' fields, then the op and where
+// the image's statistics and table lie in the workspace (byte offsets).  The
+// statistics of an image are kToneStatWords uint32: the histograms of q0, q1,
+// q2 and, used by MXD_TONE_CONTRAST only, of the luma byte; they must be zero
+// when tone_hist starts.
+constexpr int kToneHistRows = 16;
+constexpr int kToneStatWords = 4 * 256;
+constexpr int kToneLutBytes = 3 * 256;
+struct ToneRowDev {
+  const uint8_t* src;  // u8 rows: 16-byte aligned base, src_stride a multiple of 16
+  void* dst;
+  int64_t src_stride, dst_stride;
+  int32_t crop_w, crop_h, channels;
+  int32_t blk_begin;
+  float m[12];         // mxd_color::m, row-major (the identity without colours)
+  int32_t op, arg;     // mxd_tone::op, ::arg
+  float factor;        // mxd_tone::factor
+  int32_t hist_begin;  // first of the image's tone_hist workgroups (the next image's when it has none)
+  int32_t stat_off;    // the image's statistics in the workspace, -1: the op needs none
+  int32_t lut_off;     // the image's table in the workspace
+  int32_t pad[2];
+};
+static_assert(sizeof(ToneRowDev) == 128, "ToneRowDev layout");
+static_assert(offsetof(ToneRowDev, op) == sizeof(ColorRowDev), "ToneRowDev starts with ColorRowDev's fields");
+// ws: the workspace's device address; matrix: some image has a colour matrix
+// (else the entries hold the identity and the step is skipped).
+int launch_tone(const ToneRowDev* rows, int nimgs, int hist_blocks, int row_blocks, const OutFmtDev& fmt, uint8_t* ws,
+                bool matrix, void* stream);
+// Whether op reads the image's statistics.
+inline bool tone_needs_stats(int op) { return op >= 3; }
 // Waves of this configuration the device runs at once (occupancy x CUs), 0 if unknown.
 int wave_capacity(const WaveCfg& cfg, int device);
 // Diagnostics: the occupancy API's blocks per CU, the kernel's VGPRs and LDS

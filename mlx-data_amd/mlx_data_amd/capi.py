@@ -44,6 +44,8 @@ EXPORTS = (
     "mxd_jpeg_resize_crop_to_device_fmt",
     "mxd_color_twist_matrix", "mxd_color_apply_u8", "mxd_resize_crop_batch_color",
     "mxd_resize_crop_to_device_color", "mxd_jpeg_resize_crop_to_device_color",
+    "mxd_tone_table_u8", "mxd_tone_apply_u8", "mxd_resize_crop_batch_tone",
+    "mxd_resize_crop_to_device_tone", "mxd_jpeg_resize_crop_to_device_tone",
 )
 
 MXD_ELEM_F32 = 0
@@ -342,6 +344,64 @@ def resize_crop_to_device_color(images, colors, n, out_dtype=MXD_U8, fmt=None, d
 
 def jpeg_resize_crop_to_device_color(images, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
     check(lib().mxd_jpeg_resize_crop_to_device_color(images, colors, n, out_dtype, _fmt_ref(fmt), device))
+
+
+MXD_TONE_NONE = 0
+MXD_TONE_POSTERIZE = 1
+MXD_TONE_SOLARIZE = 2
+MXD_TONE_AUTOCONTRAST = 3
+MXD_TONE_EQUALIZE = 4
+MXD_TONE_CONTRAST = 5
+
+
+class MxdTone(ctypes.Structure):
+    """struct mxd_tone (include/mxd_amd.h): a tone operation and its parameter."""
+
+    _fields_ = [("op", ctypes.c_int32), ("arg", ctypes.c_int32), ("factor", ctypes.c_float),
+                ("reserved", ctypes.c_int32)]
+
+
+def make_tones(tones):
+    """(op, arg, factor) tuples (or MxdTone values) -> ctypes array of mxd_tone."""
+    arr = (MxdTone * max(1, len(tones)))()
+    for i, t in enumerate(tones):
+        if isinstance(t, MxdTone):
+            arr[i] = t
+        else:
+            op, arg, factor = t
+            arr[i].op, arr[i].arg, arr[i].factor, arr[i].reserved = int(op), int(arg), float(factor), 0
+    return arr
+
+
+def tone_table_u8(rgb, tone):
+    """mxd_tone_table_u8: the (3, 256) uint8 table of `tone` for (..., 3) uint8 pixels."""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    table = np.empty((3, 256), np.uint8)
+    check(lib().mxd_tone_table_u8(rgb.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(rgb.size // 3),
+                                  make_tones([tone]), table.ctypes.data_as(ctypes.c_void_p)))
+    return table
+
+
+def tone_apply_u8(rgb, tone):
+    """mxd_tone_apply_u8: the CPU statement of a tone operation on (..., 3) uint8 pixels."""
+    rgb = np.ascontiguousarray(rgb, np.uint8)
+    out = np.empty_like(rgb)
+    check(lib().mxd_tone_apply_u8(rgb.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(rgb.size // 3),
+                                  make_tones([tone]), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def resize_crop_batch_tone(images, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0, stream=None):
+    check(lib().mxd_resize_crop_batch_tone(images, tones, colors, n, out_dtype, _fmt_ref(fmt), device,
+                                           ctypes.c_void_p(stream)))
+
+
+def resize_crop_to_device_tone(images, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_resize_crop_to_device_tone(images, tones, colors, n, out_dtype, _fmt_ref(fmt), device))
+
+
+def jpeg_resize_crop_to_device_tone(images, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_jpeg_resize_crop_to_device_tone(images, tones, colors, n, out_dtype, _fmt_ref(fmt), device))
 
 
 def set_kernel_policy(policy):

@@ -78,6 +78,25 @@ map as one more kernel behind the resize of the same call.  A resize or a
 second colour op after it materialises the first.  Bad arguments raise
 ``ValueError`` when the op is made.
 
+The tone operations that depend on the image's own content stay in the launch
+as well (the fourth addition): ``image_posterize(key, bits, output_key="")``,
+``image_solarize(key, threshold=128, output_key="")``,
+``image_autocontrast(key, output_key="")``, ``image_equalize(key,
+output_key="")`` and ``image_contrast(key, factor, output_key="")``, with
+their ``_if`` forms.  They are Pillow's ``ImageOps.posterize`` / ``solarize``
+/ ``autocontrast`` / ``equalize`` and ``ImageEnhance.Contrast`` on the uint8
+result, bit for bit (``image_contrast`` blends with the grey of the image's
+mean luma; ``image_color_twist``'s contrast keeps its fixed centre).  RGB
+images only.  The op only marks the pending image and ``batch`` runs a
+per-image histogram, a table builder and a lookup behind the resize of the
+same call.  The stage order in a launch is tone, colour, output form: a
+colour op, ``image_to_float``, ``image_normalize`` and flips compose after a
+tone op; crops compose after posterize and solarize and materialise the other
+three first (their statistics are those of the uncropped result); a resize, a
+second tone op, or a tone op after a colour op materialises what is pending.
+A video's frames each use their own statistics.  Bad arguments raise
+``ValueError`` when the op is made.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole
@@ -137,7 +156,8 @@ def _add_if_variants(cls):
     for name in ("key_transform", "load_image", "image_resize_smallest_side", "image_resize",
                  "image_center_crop", "image_random_crop", "image_random_h_flip", "image_random_area_crop",
                  "image_rotate", "image_channel_reduction", "image_to_float", "image_normalize",
-                 "image_color_twist", "image_color_matrix", "image_random_color_twist"):
+                 "image_color_twist", "image_color_matrix", "image_random_color_twist",
+                 "image_posterize", "image_solarize", "image_autocontrast", "image_equalize", "image_contrast"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 
