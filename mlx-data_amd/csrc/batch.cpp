@@ -405,47 +405,76 @@ int launch_all(const BatchLayout& L, const ImgDev* dev, Workspace* ws, const mxd
   return launch_rc;
 }
 
+// The second pass of the layout's kind over its entries in the uploaded copy.
+int launch_second_pass(const BatchLayout& L, const ImgDev* dev, const mxd::OutFmtDev& ofd, void* stream) {
+  if (L.fmt_count == 0) return MXD_OK;
+  const void* entries = dev + L.fmt_at;
+  const char* what = "format_rows launch failed: ";
+  int rc = 0;
+  if (L.pass == SecondPass::Tone) {
+    // this call's statistics start from zero, whatever the stream's last call left
+    if (L.tone_stat_bytes > 0 &&
+        hipMemsetAsync(L.tone_ws, 0, L.tone_stat_bytes, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+      return fail(MXD_ERR_DEVICE, std::string("tone workspace memset failed: ") + hipGetErrorString(hipGetLastError()));
+    what = "tone launch failed: ";
+    rc = mxd::launch_tone(static_cast<const mxd::ToneRowDev*>(entries), L.fmt_count, L.tone_hist_blocks, L.fmt_blocks, ofd,
+                          L.tone_ws, L.matrix, stream);
+  } else if (L.pass == SecondPass::Color) {
+    what = "color_rows launch failed: ";
+    rc = mxd::launch_color_rows(static_cast<const mxd::ColorRowDev*>(entries), L.fmt_count, L.fmt_blocks, ofd, stream);
+  } else {
+    rc = mxd::launch_format_rows(static_cast<const mxd::FmtRowDev*>(entries), L.fmt_count, L.fmt_blocks, ofd, stream);
+  }
+  if (rc) return fail(MXD_ERR_DEVICE, std::string(what) + hipGetErrorString(hipGetLastError()));
+  return MXD_OK;
+}
+
 // One launchable batch: its layout, the upload, the launches.
 int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-                   const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones) {
+                   const Stored* stored, const PostOps& ops) {
   DeviceGuard guard(device);
   BatchLayout L;
-  if (int rc = build_layout(device_env(), device, images, n, stored, out_dtype, fmt, &L, colors, tones)) return rc;
+  if (int rc = build_layout(device_env(), device, images, n, stored, out_dtype, ops, &L)) return rc;
   mxd::OutFmtDev ofd{};
   std::unique_lock<std::mutex> scratch_hold;
-  if (fmt || colors || tones)
-    if (int rc = take_scratch(L, fmt, device, stream, &ofd, &scratch_hold)) return rc;
+  if (ops.any())
+    if (int rc = take_scratch(L, ops.fmt, device, stream, &ofd, &scratch_hold)) return rc;
   ImgDev* dev = nullptr;
   std::unique_lock<std::mutex> hold;
   Workspace* ws = nullptr;
   bool hit = false;
   if (int rc = upload_descs(L.descs, device, stream, &dev, &hold, &ws, &hit)) return rc;
-  // (a colour call's resize kernels run in their u8 mode: the format is color_rows')
-  int launch_rc = launch_all(L, dev, ws, fmt && !colors && !tones ? &ofd : nullptr, stream);
-  // The second pass of a formatted call, behind the joins: every resize
-  // kernel that wrote scratch rows is ordered before it on the caller's stream.
-  if (launch_rc == MXD_OK && tones) {
-    // this call's statistics start from zero, whatever the stream's last call left
-    if (L.tone_stat_bytes > 0 &&
-        hipMemsetAsync(L.tone_ws, 0, L.tone_stat_bytes, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
-      launch_rc = fail(MXD_ERR_DEVICE, std::string("tone workspace memset failed: ") + hipGetErrorString(hipGetLastError()));
-    else if (mxd::launch_tone(reinterpret_cast<const mxd::ToneRowDev*>(dev + L.fmt_at), L.fmt_count, L.tone_hist_blocks,
-                              L.fmt_blocks, ofd, L.tone_ws, L.tone_matrix, stream))
-      launch_rc = fail(MXD_ERR_DEVICE, std::string("tone launch failed: ") + hipGetErrorString(hipGetLastError()));
-  } else if (launch_rc == MXD_OK && colors) {
-    if (mxd::launch_color_rows(reinterpret_cast<const mxd::ColorRowDev*>(dev + L.fmt_at), L.fmt_count, L.fmt_blocks, ofd,
-                               stream))
-      launch_rc = fail(MXD_ERR_DEVICE, std::string("color_rows launch failed: ") + hipGetErrorString(hipGetLastError()));
-  } else if (launch_rc == MXD_OK && L.fmt_count > 0 &&
-      mxd::launch_format_rows(reinterpret_cast<const mxd::FmtRowDev*>(dev + L.fmt_at), L.fmt_count, L.fmt_blocks, ofd,
-                              stream))
-    launch_rc = fail(MXD_ERR_DEVICE, std::string("format_rows launch failed: ") + hipGetErrorString(hipGetLastError()));
+  int launch_rc = launch_all(L, dev, ws, ops.resize_formats() ? &ofd : nullptr, stream);
+  // The second pass, behind the joins: every resize kernel that wrote scratch
+  // rows is ordered before it on the caller's stream.
+  if (launch_rc == MXD_OK) launch_rc = launch_second_pass(L, dev, ofd, stream);
   // The batch is counted on a failed launch too (see launch_all).
   const int rel = release_descs(ws, stream, hit);
   return launch_rc != MXD_OK ? launch_rc : rel;
 }
 
 }  // namespace
+
+int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* out_dtype, mxd_out_format* f32_fmt) {
+  if (!ops->per_image()) return MXD_OK;
+  if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
+  if (ops->tones)
+    if (int rc = tone_validate(images, ops->tones, n)) return rc;
+  if (ops->colors)
+    if (int rc = color_validate(images, ops->colors, n)) return rc;
+  if (!ops->fmt) {
+    if (*out_dtype != MXD_U8 && *out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
+    if (*out_dtype == MXD_F32_DIV255) {
+      // the table of {F32, HWC, normalize 0}: q / 255 bit for bit
+      *f32_fmt = mxd_out_format{};
+      f32_fmt->elem = MXD_ELEM_F32;
+      f32_fmt->layout = MXD_LAYOUT_HWC;
+      ops->fmt = f32_fmt;
+    }
+  }
+  *out_dtype = MXD_U8;  // the form every image is resized in
+  return MXD_OK;
+}
 
 // One channel count per launch, and one alpha mode per general-kernel launch.
 std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stored* stored) {
@@ -462,21 +491,18 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 }
 
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored, const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones) {
+              const Stored* stored, PostOps ops) {
   mxd_out_format f32_fmt;
-  if (tones) {
-    if (int rc = tone_prepare(images, tones, colors, n, &out_dtype, &fmt, &f32_fmt)) return rc;
-  } else if (colors)
-    if (int rc = color_prepare(images, colors, n, &out_dtype, &fmt, &f32_fmt)) return rc;
-  if (int rc = validate_batch(images, n, &out_dtype, device, fmt)) return rc;
+  if (int rc = prepare_post_ops(images, n, &ops, &out_dtype, &f32_fmt)) return rc;
+  if (int rc = validate_batch(images, n, &out_dtype, device, ops.fmt)) return rc;
   if (n == 0) return MXD_OK;
   // (a colour or tone call's images all have three channels: one launchable
   // batch, so colors[i] and tones[i] stay beside images[i])
-  const std::vector<SubBatch> subs = colors || tones ? std::vector<SubBatch>{} : split_batch(images, n, stored);
-  if (subs.empty()) return run_launchable(images, n, out_dtype, device, stream, stored, fmt, colors, tones);
+  const std::vector<SubBatch> subs = ops.per_image() ? std::vector<SubBatch>{} : split_batch(images, n, stored);
+  if (subs.empty()) return run_launchable(images, n, out_dtype, device, stream, stored, ops);
   for (const SubBatch& s : subs)
     if (int rc = run_launchable(s.images.data(), (int32_t)s.images.size(), out_dtype, device, stream,
-                                stored ? s.stored.data() : nullptr, fmt, nullptr, nullptr))
+                                stored ? s.stored.data() : nullptr, ops))
       return rc;
   return MXD_OK;
 }

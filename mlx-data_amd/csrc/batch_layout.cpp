@@ -317,39 +317,39 @@ int general_group(Batch& b) {
   return MXD_OK;
 }
 
-// Formatted call: the wave images' destinations are the caller's; the others
-// get their scratch rows (at 256-byte aligned offsets: add_scratch).
-void place_formatted(Batch& b, const mxd_image* callers) {
+// Whether the second pass reads image i (from scratch rows): every image,
+// but a formatted call's wave images, which the resize launch formats.
+bool second_pass_reads(const Batch& b, int32_t i) { return !(b.formatted && b.L.plans[i].wave); }
+
+// The images the second pass reads get their scratch rows (at 256-byte
+// aligned offsets: add_scratch); the others keep the caller's destination.
+void place_scratch(Batch& b, const mxd_image* callers) {
   size_t at = 0;
   for (int32_t i = 0; i < b.n; i++) {
     mxd_image& im = b.L.images[i];
-    if (b.L.plans[i].wave) {
-      im.dst = callers[i].dst;
-      im.dst_stride = callers[i].dst_stride;
-    } else {
+    if (second_pass_reads(b, i)) {
       im.dst = reinterpret_cast<void*>(at);
       at += scratch_size(im);
+    } else {
+      im.dst = callers[i].dst;
+      im.dst_stride = callers[i].dst_stride;
     }
   }
   b.L.scratch_bytes = at;
 }
 
-// Colour call: every image's rows go to the scratch.
-void place_colored(Batch& b) {
-  size_t at = 0;
-  for (int32_t i = 0; i < b.n; i++) {
-    mxd_image& im = b.L.images[i];
-    im.dst = reinterpret_cast<void*>(at);
-    at += scratch_size(im);
-  }
-  b.L.scratch_bytes = at;
+// The head of an entry: scratch rows `im` to the caller's destination.
+mxd::FmtRowDev entry_head(const mxd_image& im, const mxd_image& caller, int32_t blk_begin) {
+  return mxd::FmtRowDev{static_cast<const uint8_t*>(im.dst), caller.dst, im.dst_stride, caller.dst_stride,
+                        im.crop_w, im.crop_h, im.channels, blk_begin};
 }
 
 // After every descriptor, in ImgDev-sized blocks: the unit -> image tables of
-// the band launches whose images differ in unit count (int32 each), then
-// format_rows' entries: part of the upload's bytes, so a cached slot is
-// reused only with the same scratch rows and destinations.
-void append_tables(Batch& b, const mxd_image* callers, const mxd_color* colors, const mxd_tone* tones) {
+// the band launches whose images differ in unit count (int32 each), then the
+// second pass's entries: part of the upload's bytes, so a cached slot is
+// reused only with the same scratch rows and destinations (and matrices, ops
+// and parameters).
+void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
   BatchLayout& L = b.L;
   std::vector<int32_t> unit_tables;
   for (BatchLayout::BandGroup& g : L.bands) {
@@ -366,73 +366,38 @@ void append_tables(Batch& b, const mxd_image* callers, const mxd_color* colors, 
   if (!unit_tables.empty())
     std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.tables_at), unit_tables.data(), unit_tables.size() * 4);
   L.fmt_at = L.descs.size();
-  if (tones) {
-    // tone_rows' entries, in batch order: ops, parameters and matrices are
-    // part of the upload's bytes, so a cached slot is reused only for the
-    // same ones.  The workspace follows the scratch rows: statistics first.
-    std::vector<mxd::ToneRowDev> rows(b.n);
-    int32_t stats = 0;
-    for (int32_t i = 0; i < b.n; i++) {
-      const mxd_image& im = L.images[i];
-      mxd::ToneRowDev& r = rows[i];
-      r = mxd::ToneRowDev{};
-      r.src = static_cast<const uint8_t*>(im.dst), r.dst = callers[i].dst;
-      r.src_stride = im.dst_stride, r.dst_stride = callers[i].dst_stride;
-      r.crop_w = im.crop_w, r.crop_h = im.crop_h, r.channels = im.channels;
-      r.blk_begin = L.fmt_blocks;
-      for (int k = 0; k < 12; k++) r.m[k] = colors ? color_entry(colors[i].m[k / 4][k % 4]) : k % 5 == 0 ? 1.0f : 0.0f;
-      r.op = tones[i].op, r.arg = tones[i].arg, r.factor = tones[i].factor;
-      r.hist_begin = L.tone_hist_blocks;
-      r.stat_off = -1;
-      if (mxd::tone_needs_stats(r.op)) {
-        r.stat_off = stats * (int32_t)(mxd::kToneStatWords * sizeof(uint32_t));
-        stats++;
-        L.tone_hist_blocks += (im.crop_h + mxd::kToneHistRows - 1) / mxd::kToneHistRows;
-      }
-      L.fmt_blocks += (im.crop_h + mxd::kColorRows - 1) / mxd::kColorRows;
-    }
-    L.tone_stat_bytes = (size_t)stats * mxd::kToneStatWords * sizeof(uint32_t);
-    for (int32_t i = 0; i < b.n; i++) rows[i].lut_off = (int32_t)(L.tone_stat_bytes + (size_t)i * mxd::kToneLutBytes);
-    L.tone_matrix = colors != nullptr;
-    L.tone_ws_at = (L.scratch_bytes + 255) & ~(size_t)255;
-    L.scratch_bytes = L.tone_ws_at + L.tone_stat_bytes + (size_t)b.n * mxd::kToneLutBytes;
-    L.fmt_count = b.n;
-    const size_t bytes = rows.size() * sizeof(mxd::ToneRowDev);
-    L.descs.resize(L.fmt_at + (bytes + sizeof(ImgDev) - 1) / sizeof(ImgDev));
-    std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.fmt_at), rows.data(), bytes);
-    return;
-  }
-  if (colors) {
-    // color_rows' entries, in batch order: the matrices are part of the
-    // upload's bytes, so a cached slot is reused only for the same matrices.
-    std::vector<mxd::ColorRowDev> rows(b.n);
-    for (int32_t i = 0; i < b.n; i++) {
-      const mxd_image& im = L.images[i];
-      mxd::ColorRowDev& r = rows[i];
-      r = mxd::ColorRowDev{static_cast<const uint8_t*>(im.dst), callers[i].dst, im.dst_stride, callers[i].dst_stride,
-                           im.crop_w, im.crop_h, im.channels, L.fmt_blocks, {}};
-      for (int k = 0; k < 12; k++) r.m[k] = color_entry(colors[i].m[k / 4][k % 4]);
-      L.fmt_blocks += (im.crop_h + mxd::kColorRows - 1) / mxd::kColorRows;
-    }
-    L.fmt_count = b.n;
-    const size_t bytes = rows.size() * sizeof(mxd::ColorRowDev);
-    L.descs.resize(L.fmt_at + (bytes + sizeof(ImgDev) - 1) / sizeof(ImgDev));
-    std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.fmt_at), rows.data(), bytes);
-    return;
-  }
-  if (!b.formatted) return;
-  std::vector<mxd::FmtRowDev> rows;
-  for (int32_t i = 0; i < b.n; i++) {
+  if (L.pass == SecondPass::None) return;
+  for (int32_t i = 0; i < b.n; i++) L.fmt_count += second_pass_reads(b, i) ? 1 : 0;
+  L.descs.resize(L.fmt_at + ((size_t)L.fmt_count * L.entry_size + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
+  const int32_t block_rows = L.pass == SecondPass::Format ? mxd::kFmtRows : mxd::kPixelRows;
+  int32_t stats = 0;
+  for (int32_t i = 0, j = 0; i < b.n; i++) {
+    if (!second_pass_reads(b, i)) continue;
     const mxd_image& im = L.images[i];
-    if (L.plans[i].wave) continue;
-    rows.push_back(mxd::FmtRowDev{static_cast<const uint8_t*>(im.dst), callers[i].dst, im.dst_stride,
-                                  callers[i].dst_stride, im.crop_w, im.crop_h, im.channels, L.fmt_blocks});
-    L.fmt_blocks += (im.crop_h + mxd::kFmtRows - 1) / mxd::kFmtRows;
+    mxd::FmtRowDev& head = L.entry(j++);
+    head = entry_head(im, callers[i], L.fmt_blocks);
+    L.fmt_blocks += (im.crop_h + block_rows - 1) / block_rows;
+    if (L.pass == SecondPass::Format) continue;
+    mxd::ColorRowDev& c = reinterpret_cast<mxd::ColorRowDev&>(head);
+    for (int k = 0; k < 12; k++) c.m[k] = ops.colors ? color_entry(ops.colors[i].m[k / 4][k % 4]) : k % 5 == 0 ? 1.0f : 0.0f;
+    if (L.pass == SecondPass::Color) continue;
+    // The workspace follows the scratch rows: statistics first.
+    mxd::ToneRowDev& t = reinterpret_cast<mxd::ToneRowDev&>(head);
+    t.op = ops.tones[i].op, t.arg = ops.tones[i].arg, t.factor = ops.tones[i].factor;
+    t.hist_begin = L.tone_hist_blocks;
+    t.stat_off = -1;
+    if (mxd::tone_needs_stats(t.op)) {
+      t.stat_off = stats * (int32_t)(mxd::kToneStatWords * sizeof(uint32_t));
+      stats++;
+      L.tone_hist_blocks += (im.crop_h + mxd::kToneHistRows - 1) / mxd::kToneHistRows;
+    }
   }
-  L.fmt_count = (int32_t)rows.size();
-  const size_t bytes = rows.size() * sizeof(mxd::FmtRowDev);
-  L.descs.resize(L.fmt_at + (bytes + sizeof(ImgDev) - 1) / sizeof(ImgDev));
-  if (bytes) std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.fmt_at), rows.data(), bytes);
+  if (L.pass != SecondPass::Tone) return;
+  L.tone_stat_bytes = (size_t)stats * mxd::kToneStatWords * sizeof(uint32_t);
+  for (int32_t i = 0; i < b.n; i++)
+    reinterpret_cast<mxd::ToneRowDev&>(L.entry(i)).lut_off = (int32_t)(L.tone_stat_bytes + (size_t)i * mxd::kToneLutBytes);
+  L.tone_ws_at = (L.scratch_bytes + 255) & ~(size_t)255;
+  L.scratch_bytes = L.tone_ws_at + L.tone_stat_bytes + (size_t)b.n * mxd::kToneLutBytes;
 }
 
 }  // namespace
@@ -444,36 +409,31 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity) {
 
 void BatchLayout::add_scratch(uint8_t* base) {
   for (int32_t k = 0; k < n; k++)
-    if (colored || toned || !plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
-  if (toned) {
-    for (int32_t j = 0; j < fmt_count; j++) tone_rows()[j].src = base + reinterpret_cast<uintptr_t>(tone_rows()[j].src);
-    tone_ws = base + tone_ws_at;
-    return;
-  }
-  if (colored) {
-    for (int32_t j = 0; j < fmt_count; j++)
-      color_rows()[j].src = base + reinterpret_cast<uintptr_t>(color_rows()[j].src);
-    return;
-  }
-  for (int32_t j = 0; j < fmt_count; j++) fmt_rows()[j].src = base + reinterpret_cast<uintptr_t>(fmt_rows()[j].src);
+    if (pass != SecondPass::Format || !plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
+  for (int32_t j = 0; j < fmt_count; j++) entry(j).src = base + reinterpret_cast<uintptr_t>(entry(j).src);
+  if (pass == SecondPass::Tone) tone_ws = base + tone_ws_at;
 }
 
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
-                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors,
-                 const mxd_tone* tones) {
+                 int32_t out_dtype, const PostOps& ops, BatchLayout* out) {
   *out = BatchLayout{};
   BatchLayout& L = *out;
   L.n = n;
-  L.toned = tones != nullptr;
-  L.colored = colors != nullptr && !tones;
+  L.pass = ops.pass();
+  L.entry_size = L.pass == SecondPass::Tone    ? sizeof(mxd::ToneRowDev)
+                 : L.pass == SecondPass::Color ? sizeof(mxd::ColorRowDev)
+                 : L.pass == SecondPass::Format ? sizeof(mxd::FmtRowDev)
+                                                : 0;
+  L.matrix = ops.colors != nullptr;
   // A formatted call plans its kernels as a u8 call does: the wave kernels
   // exist in the same shapes in every output mode and write any element
   // alignment, and an image they do not take is resized into u8 scratch rows
   // (16-byte aligned; placed once the plans are known).
   const mxd_image* const callers = images;
-  // A colour call plans every image so, and keeps every u8 kernel a plain u8
-  // call has (the cubic filters' and JPEG plane sources' wave kernels too).
-  if (fmt || colors || tones) {
+  // A colour or tone call plans every image so, and keeps every u8 kernel a
+  // plain u8 call has (the cubic filters' and JPEG plane sources' wave
+  // kernels too).
+  if (ops.any()) {
     out_dtype = MXD_U8;
     L.images.assign(images, images + n);
     for (mxd_image& im : L.images) {
@@ -482,10 +442,9 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
     }
     images = L.images.data();
   }
-  Batch b{env, device, images, stored, n, images[0].channels, out_dtype, fmt != nullptr && !colors && !tones, L, {}};
+  Batch b{env, device, images, stored, n, images[0].channels, out_dtype, ops.resize_formats(), L, {}};
   if (int rc = plan_images(b)) return rc;
-  if (colors || tones) place_colored(b);
-  else if (fmt) place_formatted(b, callers);
+  if (ops.any()) place_scratch(b, callers);
   // Descriptors of one upload: band-kernel images first, then wave-kernel
   // images, then the general kernel's.
   L.descs.resize(n);
@@ -493,7 +452,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = band_groups(b)) return rc;
   if (int rc = wave_groups(b)) return rc;
   if (int rc = general_group(b)) return rc;
-  append_tables(b, callers, colors, tones);
+  append_tables(b, callers, ops);
   // Largest first (a band unit is a workgroup, ~4 wave units).
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});

@@ -161,6 +161,19 @@ int run_pixmap(const mxd_pixmap* images, int32_t n, int32_t op, int32_t device, 
 
 using namespace mxd::capi;
 
+// The head of the _color (tones == nullptr, tone_call false) and _tone entry
+// points: the format when there is one, the call's own array; an empty call
+// keeps the format alone.
+static int post_ops(const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones, bool tone_call, int32_t n,
+                    PostOps* ops) {
+  if (fmt)
+    if (int rc = fmt_validate(fmt, 0)) return rc;
+  if (n > 0 && !tone_call && !colors) return fail(MXD_ERR_INVALID, "mxd: null colors");
+  if (n > 0 && tone_call && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
+  *ops = n > 0 ? PostOps{fmt, colors, tones} : PostOps{fmt};
+  return MXD_OK;
+}
+
 extern "C" {
 
 int mxd_abi_version(void) { return MXD_ABI_VERSION; }
@@ -247,25 +260,22 @@ int mxd_resize_crop_batch(const mxd_image* images, int32_t n, int32_t out_dtype,
 int mxd_resize_crop_batch_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device,
                               void* stream) {
   if (int rc = fmt_validate(fmt, 0)) return rc;
-  return run_batch(images, n, MXD_U8, device, stream, nullptr, fmt);
+  return run_batch(images, n, MXD_U8, device, stream, nullptr, PostOps{fmt});
 }
 
+// (an empty call with a format: run_batch plans it in MXD_U8 whatever out_dtype says)
 int mxd_resize_crop_batch_color(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t out_dtype,
                                 const mxd_out_format* fmt, int32_t device, void* stream) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !colors) return fail(MXD_ERR_INVALID, "mxd: null colors");
-  if (n <= 0) return run_batch(images, n, fmt ? MXD_U8 : out_dtype, device, stream, nullptr, fmt);
-  return run_batch(images, n, out_dtype, device, stream, nullptr, fmt, colors);
+  PostOps ops;
+  if (int rc = post_ops(fmt, colors, nullptr, false, n, &ops)) return rc;
+  return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
 int mxd_resize_crop_batch_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
                                int32_t out_dtype, const mxd_out_format* fmt, int32_t device, void* stream) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
-  if (n <= 0) return run_batch(images, n, fmt ? MXD_U8 : out_dtype, device, stream, nullptr, fmt);
-  return run_batch(images, n, out_dtype, device, stream, nullptr, fmt, colors, tones);
+  PostOps ops;
+  if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
 int mxd_set_kernel_policy(int32_t policy) { return g_policy.exchange(policy); }
@@ -460,23 +470,21 @@ int mxd_resize_crop_to_device(const mxd_image* images, int32_t n, int32_t out_dt
 
 int mxd_resize_crop_to_device_color(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t out_dtype,
                                     const mxd_out_format* fmt, int32_t device) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !colors) return fail(MXD_ERR_INVALID, "mxd: null colors");
-  return host_path(images, n, out_dtype, device, true, nullptr, fmt, n > 0 ? colors : nullptr);
+  PostOps ops;
+  if (int rc = post_ops(fmt, colors, nullptr, false, n, &ops)) return rc;
+  return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
 int mxd_resize_crop_to_device_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
                                    int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
-  return host_path(images, n, out_dtype, device, true, nullptr, fmt, n > 0 ? colors : nullptr, n > 0 ? tones : nullptr);
+  PostOps ops;
+  if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
 int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device) {
   if (int rc = fmt_validate(fmt, 0)) return rc;
-  return host_path(images, n, MXD_U8, device, true, nullptr, fmt);
+  return host_path(images, n, MXD_U8, device, true, nullptr, PostOps{fmt});
 }
 
 int mxd_memcpy_h2d(void* dst, const void* src, size_t bytes, int32_t device) {
@@ -572,24 +580,22 @@ int mxd_jpeg_resize_crop_to_device(const mxd_jpeg_image* images, int32_t n, int3
 
 int mxd_jpeg_resize_crop_to_device_color(const mxd_jpeg_image* images, const mxd_color* colors, int32_t n,
                                          int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !colors) return fail(MXD_ERR_INVALID, "mxd: null colors");
-  return jpeg_path(images, n, out_dtype, device, true, fmt, n > 0 ? colors : nullptr);
+  PostOps ops;
+  if (int rc = post_ops(fmt, colors, nullptr, false, n, &ops)) return rc;
+  return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 
 int mxd_jpeg_resize_crop_to_device_tone(const mxd_jpeg_image* images, const mxd_tone* tones, const mxd_color* colors,
                                         int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
-  return jpeg_path(images, n, out_dtype, device, true, fmt, n > 0 ? colors : nullptr, n > 0 ? tones : nullptr);
+  PostOps ops;
+  if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 
 int mxd_jpeg_resize_crop_to_device_fmt(const mxd_jpeg_image* images, int32_t n, const mxd_out_format* fmt,
                                        int32_t device) {
   if (int rc = fmt_validate(fmt, 0)) return rc;
-  return jpeg_path(images, n, MXD_U8, device, true, fmt);
+  return jpeg_path(images, n, MXD_U8, device, true, PostOps{fmt});
 }
 
 int mxd_host_stats(int64_t* out6, int32_t reset) {

@@ -262,6 +262,36 @@ struct LayoutEnv {
 LayoutEnv device_env();
 LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
 
+// What follows the resize of a call, as every layer below the entry points
+// passes it on.  fmt: a formatted output (mxd_out_format).  colors: a colour
+// call, colors[i] belongs to images[i].  tones: a tone call, tones[i] belongs
+// to images[i]; colors may be null then (no matrix).
+// The second pass (row_stage.hip) such a call launches behind its resize
+// kernels: format_rows for the images of a formatted call that no wave kernel
+// takes, pixel_rows for every image of a colour or tone call.
+enum class SecondPass : int32_t { None, Format, Color, Tone };
+struct PostOps {
+  const mxd_out_format* fmt = nullptr;
+  const mxd_color* colors = nullptr;
+  const mxd_tone* tones = nullptr;
+  // (a format alone, or nullptr, converts: a formatted / plain call)
+  PostOps(const mxd_out_format* f = nullptr, const mxd_color* c = nullptr, const mxd_tone* t = nullptr)
+      : fmt(f), colors(c), tones(t) {}
+  bool any() const { return fmt || colors || tones; }
+  bool per_image() const { return colors || tones; }  // a colour or tone call
+  SecondPass pass() const {
+    return tones ? SecondPass::Tone : colors ? SecondPass::Color : fmt ? SecondPass::Format : SecondPass::None;
+  }
+  // The resize kernels write the format themselves (wave kernels in their
+  // formatted mode).  A colour or tone call's run in their u8 mode into
+  // scratch rows: the output form is pixel_rows' alone.
+  bool resize_formats() const { return pass() == SecondPass::Format; }
+  // The call's share for the images from `first` on (a host-path chunk).
+  PostOps at(int32_t first) const {
+    return PostOps{fmt, colors ? colors + first : nullptr, tones ? tones + first : nullptr};
+  }
+};
+
 struct BatchLayout {
   struct BandGroup {
     int32_t first, count, units;  // first descriptor, images, units
@@ -281,7 +311,7 @@ struct BatchLayout {
   std::vector<ImgPlan> plans;     // by batch index
   std::vector<int32_t> image_of;  // batch index of descriptor k < n: band, then wave, then general images
   // One upload, in ImgDev-sized blocks: the n descriptors, the unit -> image
-  // tables from tables_at, format_rows' entries from fmt_at.
+  // tables from tables_at, the second pass's entries from fmt_at.
   std::vector<ImgDev> descs;
   size_t tables_at = 0, fmt_at = 0;
   std::vector<BandGroup> bands;
@@ -289,43 +319,39 @@ struct BatchLayout {
   int32_t general_at = 0;  // first descriptor of the general kernel
   LaunchCfg general{};     // nimgs == 0: no general launch
   std::vector<Launch> launches;  // largest first
-  // Formatted call: images no wave kernel takes are resized into u8 scratch
-  // rows and formatted by format_rows.  Their descriptors' dst and their
-  // entries' src are offsets into a scratch of scratch_bytes (add_scratch).
+  // The second pass.  The images it reads are resized into u8 scratch rows:
+  // those no wave kernel takes in a formatted call, every image (wave kernels
+  // in their u8 mode included) in a colour or tone call, whose entries stand
+  // in batch order.  Their descriptors' dst and their entries' src are
+  // offsets into a scratch of scratch_bytes (add_scratch).  fmt_count entries
+  // of entry_size bytes (an FmtRowDev, ColorRowDev or ToneRowDev each, all
+  // starting with the FmtRowDev that entry() returns), fmt_blocks workgroups.
+  SecondPass pass = SecondPass::None;
+  size_t entry_size = 0;
+  bool matrix = false;  // pixel_rows applies the entries' matrices (a tone call without colours: the identity, skipped)
   std::vector<mxd_image> images;  // the batch with the destinations the resize kernels write
   size_t scratch_bytes = 0;
   int32_t fmt_count = 0, fmt_blocks = 0;
-  mxd::FmtRowDev* fmt_rows() { return reinterpret_cast<mxd::FmtRowDev*>(descs.data() + fmt_at); }
-  // Colour call: every image is resized into u8 scratch rows (wave kernels in
-  // their u8 mode included) and color_rows writes every destination.  Its
-  // entries, one per image in batch order with the image's matrix, take
-  // format_rows' place from fmt_at (fmt_count of them, fmt_blocks workgroups).
-  bool colored = false;
-  mxd::ColorRowDev* color_rows() { return reinterpret_cast<mxd::ColorRowDev*>(descs.data() + fmt_at); }
-  // Tone call: a colour call's layout with tone_rows' entries (the image's
-  // matrix, or the identity, and its mxd_tone) in color_rows' place.  Behind
-  // the scratch rows, from tone_ws_at (a multiple of 256; counted in
-  // scratch_bytes), lies the call's workspace: tone_stat_bytes of statistics
-  // (one block per image whose op needs them; zeroed for every call), then one
-  // table per image.  tone_hist_blocks: tone_hist's workgroups.  tone_ws: the
-  // workspace's address once add_scratch() knows the scratch.
-  bool toned = false, tone_matrix = false;
+  mxd::FmtRowDev& entry(int32_t j) {
+    return *reinterpret_cast<mxd::FmtRowDev*>(reinterpret_cast<uint8_t*>(descs.data() + fmt_at) + (size_t)j * entry_size);
+  }
+  // Tone call only.  Behind the scratch rows, from tone_ws_at (a multiple of
+  // 256; counted in scratch_bytes), lies the call's workspace: tone_stat_bytes
+  // of statistics (one block per image whose op needs them; zeroed for every
+  // call), then one table per image.  tone_hist_blocks: tone_hist's
+  // workgroups.  tone_ws: the workspace's address once add_scratch() knows
+  // the scratch.
   size_t tone_ws_at = 0, tone_stat_bytes = 0;
   int32_t tone_hist_blocks = 0;
   uint8_t* tone_ws = nullptr;
-  mxd::ToneRowDev* tone_rows() { return reinterpret_cast<mxd::ToneRowDev*>(descs.data() + fmt_at); }
   const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
   void add_scratch(uint8_t* base);
 };
-// fmt != nullptr: a formatted call (out_dtype is not read; the format's values
-// are launch arguments, not part of the layout).  colors != nullptr: a colour
-// call (colors[i] belongs to images[i]; planned as a u8 call into scratch
-// whatever fmt and out_dtype say: the output form is color_rows' alone).
-// tones != nullptr: a tone call (tones[i] belongs to images[i]; colors may be
-// null then: no matrix); planned like a colour call.
+// ops.fmt: out_dtype is not read; the format's values are launch arguments,
+// not part of the layout.  A colour or tone call is planned as a u8 call into
+// scratch whatever ops.fmt and out_dtype say.
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
-                 int32_t out_dtype, const mxd_out_format* fmt, BatchLayout* out, const mxd_color* colors = nullptr,
-                 const mxd_tone* tones = nullptr);
+                 int32_t out_dtype, const PostOps& ops, BatchLayout* out);
 
 // The images of a batch for which pred holds, in batch order, with their
 // stored entries.
@@ -351,16 +377,21 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 // Batches (batch.cpp): one fused launch per kernel shape over a batch whose
 // sources are in device memory (or, from the host path, staged: stored[i]):
 // validation, split_batch, build_layout, then upload and launches.
-// fmt != nullptr: a formatted output (out_dtype is not read).  Images a wave
+// ops.fmt alone: a formatted output (out_dtype is not read).  Images a wave
 // kernel takes are written in that form by the resize launch; the others are
 // resized into a per-(device, stream) u8 scratch and formatted by one
 // format_rows launch that follows on the stream.
-// colors != nullptr: a colour call; fmt == nullptr then means out_dtype's form
-// (MXD_U8 / MXD_F32_DIV255).  Every image is resized into the scratch in u8
-// and one color_rows launch writes the destinations.
+// ops.colors / ops.tones: a colour / tone call; ops.fmt == nullptr then means
+// out_dtype's form (MXD_U8 / MXD_F32_DIV255).  Every image is resized into the
+// scratch in u8 and the row stage (a tone call: tone_hist, tone_lut, then
+// pixel_rows) writes the destinations.
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
-              const Stored* stored = nullptr, const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr,
-              const mxd_tone* tones = nullptr);
+              const Stored* stored = nullptr, PostOps ops = {});
+// The head of every colour and tone call (nothing to do for the others):
+// validates the tones, then the matrices, makes ops->fmt the format pixel_rows
+// writes (f32_fmt, the q / 255 table, for MXD_F32_DIV255; null stays null for
+// MXD_U8) and *out_dtype the form the kernels are planned in.
+int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* out_dtype, mxd_out_format* f32_fmt);
 
 // ---------------------------------------------------------------------------
 // Colour transform (color.cpp).
@@ -368,22 +399,11 @@ int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
 float color_entry(float m);
 // colors[i] against images[i] (images may be null: the matrices alone).
 int color_validate(const mxd_image* images, const mxd_color* colors, int32_t n);
-// The head of every colour call: validates the matrices, makes *fmt the
-// format color_rows writes (f32_fmt, the q / 255 table, for MXD_F32_DIV255;
-// null stays null for MXD_U8) and *out_dtype the form the kernels are planned in.
-int color_prepare(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t* out_dtype,
-                  const mxd_out_format** fmt, mxd_out_format* f32_fmt);
 
 // ---------------------------------------------------------------------------
-// Tone operations (tone.cpp).  run_batch's tones != nullptr: a tone call;
-// every image is resized into the scratch in u8, then tone_hist, tone_lut and
-// tone_rows run on the call's stream (colors may be null: no matrix).
+// Tone operations (tone.cpp).
 // tones[i] against images[i] (images may be null: the tones alone).
 int tone_validate(const mxd_image* images, const mxd_tone* tones, int32_t n);
-// The head of every tone call: color_prepare with the tones' validation (and
-// the colours' when there are any).
-int tone_prepare(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t* out_dtype,
-                 const mxd_out_format** fmt, mxd_out_format* f32_fmt);
 
 // ---------------------------------------------------------------------------
 // Formatted outputs (outfmt.cpp).
@@ -400,14 +420,12 @@ int fmt_device_table(int32_t device, const mxd_out_format& fmt, int32_t channels
 // ---------------------------------------------------------------------------
 // Host-resident batches (hostpath.cpp; JPEG batches: hostjpeg.cpp; what
 // those two share is in hostpath.h).
-// fmt != nullptr (device destinations only): every chunk's launch writes that format.
-// colors != nullptr (device destinations only): every chunk's launch is a
-// colour call with the chunk's slice of the matrices.
+// ops (device destinations only): every chunk's launch writes ops.fmt, and is
+// a colour / tone call with the chunk's slice of the matrices / tones.
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_jpeg_image* jpeg = nullptr, const mxd_out_format* fmt = nullptr,
-              const mxd_color* colors = nullptr, const mxd_tone* tones = nullptr);
+              const mxd_jpeg_image* jpeg = nullptr, PostOps ops = {});
 int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_out_format* fmt = nullptr, const mxd_color* colors = nullptr, const mxd_tone* tones = nullptr);
+              PostOps ops = {});
 // mxd_host_stats counters: host-path calls, images, wall ns, device-wait ns,
 // coefficient parses, parse ns
 extern std::atomic<int64_t> g_host_stats[6];

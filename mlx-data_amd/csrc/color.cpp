@@ -1,7 +1,7 @@
 // color.cpp -- the per-image colour transform (mxd_color, capi_internal.h):
 // the twist matrix (brightness, contrast, saturation, hue), the CPU statement
 // of the map on result bytes, and the validation of the _color calls.  The
-// device side is color_rows.hip.  Host only.
+// device side is row_stage.hip.  Host only.
 #include "capi_internal.h"
 
 namespace mxd {
@@ -71,24 +71,6 @@ int color_validate(const mxd_image* images, const mxd_color* colors, int32_t n) 
                                            "] is not finite or larger than 1e6 (image " + std::to_string(i) + ")");
       }
   }
-  return MXD_OK;
-}
-
-int color_prepare(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t* out_dtype,
-                  const mxd_out_format** fmt, mxd_out_format* f32_fmt) {
-  if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
-  if (int rc = color_validate(images, colors, n)) return rc;
-  if (!*fmt) {
-    if (*out_dtype != MXD_U8 && *out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
-    if (*out_dtype == MXD_F32_DIV255) {
-      // the table of {F32, HWC, normalize 0}: q / 255 bit for bit
-      *f32_fmt = mxd_out_format{};
-      f32_fmt->elem = MXD_ELEM_F32;
-      f32_fmt->layout = MXD_LAYOUT_HWC;
-      *fmt = f32_fmt;
-    }
-  }
-  *out_dtype = MXD_U8;  // the form every image is resized in
   return MXD_OK;
 }
 

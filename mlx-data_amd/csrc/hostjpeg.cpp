@@ -416,7 +416,7 @@ int jpeg_enqueue(HostCall& c) {
 }
 
 int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones) {
+              PostOps ops) {
   if (n < 0 || (n > 0 && !jimg)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
   std::vector<mxd_image> imgs(n);
   for (int32_t i = 0; i < n; i++) {
@@ -448,7 +448,7 @@ int jpeg_path(const mxd_jpeg_image* jimg, int32_t n, int32_t out_dtype, int32_t 
     m.dst = j.dst;
     m.dst_stride = j.dst_stride;
   }
-  return host_path(imgs.data(), n, out_dtype, device, dst_device, jimg, fmt, colors, tones);
+  return host_path(imgs.data(), n, out_dtype, device, dst_device, jimg, ops);
 }
 
 }  // namespace capi

@@ -553,10 +553,10 @@ int resize(HostCall& c) {
   bool mixed = false;
   for (int32_t i = first + 1; i < c.cur.end; i++) mixed = mixed || c.st[i].narrow != c.st[first].narrow;
   if (!mixed)
-    return run_batch(c.dev_imgs.data(), cn, c.launch_dtype(first), c.device, c.sl->stream, c.where.data(), c.fmt,
-                     c.colors ? c.colors + first : nullptr, c.tones ? c.tones + first : nullptr);
+    return run_batch(c.dev_imgs.data(), cn, c.launch_dtype(first), c.device, c.sl->stream, c.where.data(),
+                     c.ops.at(first));
   // (narrowing needs host destinations, a format, a colour or a tone device ones: never both)
-  if (c.fmt || c.colors || c.tones) return fail(MXD_ERR_UNSUPPORTED, "mxd: narrow return within a formatted call");
+  if (c.ops.any()) return fail(MXD_ERR_UNSUPPORTED, "mxd: narrow return within a formatted call");
   int rc = MXD_OK;
   for (int part = 0; part < 2 && rc == MXD_OK; part++) {
     std::vector<mxd_image> pi;
@@ -673,16 +673,14 @@ int raw_enqueue_copies(HostCall& c) {
 // chunk's kernels first decode them into dev_mid.  Every step is common to
 // both sources unless it picks a raw_* or a jpeg_* function.
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
-              const mxd_jpeg_image* jpeg, const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones) {
+              const mxd_jpeg_image* jpeg, PostOps ops) {
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
+  // the second pass writes device destinations only
+  if (!dst_device && ops.tones) return fail(MXD_ERR_UNSUPPORTED, "mxd: tone calls need device destinations");
+  if (!dst_device && ops.colors) return fail(MXD_ERR_UNSUPPORTED, "mxd: colour calls need device destinations");
   mxd_out_format f32_fmt;
-  if (tones) {
-    if (!dst_device) return fail(MXD_ERR_UNSUPPORTED, "mxd: tone calls need device destinations");
-    if (int rc = tone_prepare(images, tones, colors, n, &out_dtype, &fmt, &f32_fmt)) return rc;
-  } else if (colors) {
-    if (!dst_device) return fail(MXD_ERR_UNSUPPORTED, "mxd: colour calls need device destinations");
-    if (int rc = color_prepare(images, colors, n, &out_dtype, &fmt, &f32_fmt)) return rc;
-  }
+  if (int rc = prepare_post_ops(images, n, &ops, &out_dtype, &f32_fmt)) return rc;
+  const mxd_out_format* const fmt = ops.fmt;
   if (fmt) {
     // formatted results go to device destinations only; the launches are planned as u8 ones
     if (!dst_device) return fail(MXD_ERR_UNSUPPORTED, "mxd: formatted outputs need device destinations");
@@ -711,9 +709,7 @@ int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
   CallCount call_count(n);
   HostCall c;
   c.images = images, c.n = n, c.out_dtype = out_dtype, c.device = device, c.dst_device = dst_device, c.jpeg = jpeg;
-  c.fmt = fmt;
-  c.colors = colors;
-  c.tones = tones;
+  c.ops = ops;
 
   // Plan: inputs and outputs per image, then the chunks.
   c.st.resize(n);

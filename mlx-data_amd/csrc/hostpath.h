@@ -114,14 +114,10 @@ struct HostCall {
   int32_t n, out_dtype, device;
   bool dst_device;
   const mxd_jpeg_image* jpeg;  // not null: images[i] is jpeg[i]'s window (hostjpeg.cpp)
-  // not null: every chunk's launch writes this format into the (device)
-  // destinations; out_dtype is then MXD_U8, the form the kernels are planned in
-  const mxd_out_format* fmt = nullptr;
-  // not null: a colour call; colors[i] belongs to images[i], and a chunk's
-  // launch gets the slice of its range
-  const mxd_color* colors = nullptr;
-  // not null: a tone call (colors may be null then); sliced like colors
-  const mxd_tone* tones = nullptr;
+  // ops.fmt: every chunk's launch writes this format into the (device)
+  // destinations; out_dtype is then MXD_U8, the form the kernels are planned
+  // in.  A colour or tone call: a chunk's launch gets ops.at(its first image).
+  PostOps ops;
   std::vector<Stage> st;
   std::vector<ChunkRange> chunks;
   HostCtx* ctx = nullptr;

@@ -3,6 +3,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 namespace mxd {
 
@@ -170,13 +171,19 @@ void* wave_cubic_kernel(const WaveCfg& cfg);
 int launch_wave_fmt(const WaveCfg& cfg, const ImgDev* imgs, const OutFmtDev& fmt, void* stream);
 int wave_fmt_capacity(const WaveCfg& cfg, int device);
 bool wave_fmt_has_kernel(const WaveCfg& cfg);
-// u8 rows -> formatted rows (format_rows.hip): the second pass of the images
-// the band and general kernels resize.  rows: device array of nimgs entries;
-// one workgroup per kFmtRows rows of an image (nblocks in all, numbered
-// through blk_begin like units through ImgDev::tile_begin).
+// The row stage (row_stage.hip): the second pass behind the resize launches
+// of a formatted, colour or tone call, over u8 scratch rows.  One entry per
+// image of the pass; a workgroup takes a fixed number of rows of one image,
+// workgroups numbered through blk_begin like units through ImgDev::tile_begin.
+// The three entry types nest: FmtRowDev is the head of all of them, a colour
+// entry adds the image's matrix, a tone entry the image's op on top of that.
+//
+// u8 rows -> formatted rows (format_rows): the images the band and general
+// kernels resize in a formatted call, 1-4 channels, one workgroup per
+// kFmtRows rows.
 constexpr int kFmtRows = 8;
 struct FmtRowDev {
-  const uint8_t* src;  // u8 rows, src_stride apart
+  const uint8_t* src;  // u8 rows, src_stride apart (pixel_rows: 16-byte aligned base, stride a multiple of 16)
   void* dst;
   int64_t src_stride, dst_stride;
   int32_t crop_w, crop_h, channels;
@@ -184,48 +191,35 @@ struct FmtRowDev {
 };
 static_assert(sizeof(FmtRowDev) == 48, "FmtRowDev layout");
 int launch_format_rows(const FmtRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
-// u8 RGB rows -> colour-transformed rows in any output form (color_rows.hip):
-// the second pass of a colour call (mxd_color), whose every image is resized
-// into u8 scratch rows.  One entry per image: format_rows' fields and the
-// image's matrix (part of the uploaded bytes, so a cached descriptor slot
-// serves the same matrices only).  One workgroup per kColorRows rows of an
-// image, numbered through blk_begin.  fmt.table == nullptr: u8 output (HWC);
-// else the table's elements, as format_rows writes them.
-constexpr int kColorRows = 8;
+// u8 RGB rows -> (per-image byte table) -> (per-image matrix) -> any output
+// form (pixel_rows): the second pass of a colour call (mxd_color) and of a
+// tone call (mxd_tone), whose every image is resized into u8 scratch rows.
+// One workgroup per kPixelRows rows of an image.  fmt.table == nullptr: u8
+// output (HWC); else the table's elements, as format_rows writes them.
+constexpr int kPixelRows = 8;
+// A colour call's entry: the matrix is part of the uploaded bytes, so a
+// cached descriptor slot serves the same matrices only.
 struct ColorRowDev {
-  const uint8_t* src;  // u8 rows: 16-byte aligned base, src_stride a multiple of 16
-  void* dst;
-  int64_t src_stride, dst_stride;
-  int32_t crop_w, crop_h, channels;
-  int32_t blk_begin;
+  FmtRowDev head;
   float m[12];  // mxd_color::m, row-major
 };
 static_assert(sizeof(ColorRowDev) == 96, "ColorRowDev layout");
 int launch_color_rows(const ColorRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
-// u8 RGB rows -> per-image byte tables -> (colour matrix) -> any output form
-// (tone_rows.hip): the second pass of a tone call (mxd_tone), whose every
-// image is resized into u8 scratch rows like a colour call's.  Three launches
-// on the call's stream: tone_hist adds the histograms of the images whose op
-// needs statistics into the workspace (one workgroup per kToneHistRows rows,
-// numbered through hist_begin; none for the other images), tone_lut turns
-// every image's statistics and parameters into its 3 x 256 byte table (one
-// workgroup per image), tone_rows looks every byte up, applies the matrix and
-// writes the destinations (color_rows' structure, numbered through
-// blk_begin).  One entry per image: color_rows' fields, then the op and where
-// the image's statistics and table lie in the workspace (byte offsets).  The
-// statistics of an image are kToneStatWords uint32: the histograms of q0, q1,
-// q2 and, used by MXD_TONE_CONTRAST only, of the luma byte; they must be zero
-// when tone_hist starts.
+// A tone call: three launches on the call's stream.  tone_hist adds the
+// histograms of the images whose op needs statistics into the workspace (one
+// workgroup per kToneHistRows rows, numbered through hist_begin; none for the
+// other images), tone_lut turns every image's statistics and parameters into
+// its 3 x 256 byte table (one workgroup per image), pixel_rows looks every
+// byte up, applies the matrix and writes the destinations.  An entry says
+// where the image's statistics and table lie in the workspace (byte offsets).
+// The statistics of an image are kToneStatWords uint32: the histograms of q0,
+// q1, q2 and, used by MXD_TONE_CONTRAST only, of the luma byte; they must be
+// zero when tone_hist starts.
 constexpr int kToneHistRows = 16;
 constexpr int kToneStatWords = 4 * 256;
 constexpr int kToneLutBytes = 3 * 256;
 struct ToneRowDev {
-  const uint8_t* src;  // u8 rows: 16-byte aligned base, src_stride a multiple of 16
-  void* dst;
-  int64_t src_stride, dst_stride;
-  int32_t crop_w, crop_h, channels;
-  int32_t blk_begin;
-  float m[12];         // mxd_color::m, row-major (the identity without colours)
+  ColorRowDev color;   // m: the identity without colours
   int32_t op, arg;     // mxd_tone::op, ::arg
   float factor;        // mxd_tone::factor
   int32_t hist_begin;  // first of the image's tone_hist workgroups (the next image's when it has none)
@@ -234,7 +228,7 @@ struct ToneRowDev {
   int32_t pad[2];
 };
 static_assert(sizeof(ToneRowDev) == 128, "ToneRowDev layout");
-static_assert(offsetof(ToneRowDev, op) == sizeof(ColorRowDev), "ToneRowDev starts with ColorRowDev's fields");
+static_assert(std::is_standard_layout<ToneRowDev>::value, "an entry is addressed through its head");
 // ws: the workspace's device address; matrix: some image has a colour matrix
 // (else the entries hold the identity and the step is skipped).
 int launch_tone(const ToneRowDev* rows, int nimgs, int hist_blocks, int row_blocks, const OutFmtDev& fmt, uint8_t* ws,

@@ -1,7 +1,7 @@
 // tone.cpp -- the per-image tone operations (mxd_tone, capi_internal.h): the
 // CPU statement of the tables (mxd_tone_table_u8, mxd_tone_apply_u8) in plain
 // C++, and the validation of the _tone calls.  The device side is
-// tone_rows.hip; the two share no code.  Host only.
+// row_stage.hip; the two share no code.  Host only.
 #include "capi_internal.h"
 
 namespace mxd {
@@ -30,26 +30,6 @@ int tone_validate(const mxd_image* images, const mxd_tone* tones, int32_t n) {
       return fail(MXD_ERR_INVALID, "mxd_tone: channels must be 3 (image " + std::to_string(i) + ")");
     if (int rc = tone_check(tones[i], i)) return rc;
   }
-  return MXD_OK;
-}
-
-int tone_prepare(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t* out_dtype,
-                 const mxd_out_format** fmt, mxd_out_format* f32_fmt) {
-  if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
-  if (int rc = tone_validate(images, tones, n)) return rc;
-  if (colors)
-    if (int rc = color_validate(images, colors, n)) return rc;
-  if (!*fmt) {
-    if (*out_dtype != MXD_U8 && *out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
-    if (*out_dtype == MXD_F32_DIV255) {
-      // the table of {F32, HWC, normalize 0}: q / 255 bit for bit
-      *f32_fmt = mxd_out_format{};
-      f32_fmt->elem = MXD_ELEM_F32;
-      f32_fmt->layout = MXD_LAYOUT_HWC;
-      *fmt = f32_fmt;
-    }
-  }
-  *out_dtype = MXD_U8;  // the form every image is resized in
   return MXD_OK;
 }
 

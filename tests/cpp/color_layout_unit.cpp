@@ -64,8 +64,8 @@ int main() {
     const bool prefer_band = pass >= 2;
     mxd_set_kernel_policy(prefer_band ? MXD_POLICY_PREFER_BAND : MXD_POLICY_AUTO);
     BatchLayout L;
-    CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, f, &L, colors.data()) == MXD_OK);
-    CHECK(L.colored && L.n == n && (int32_t)L.image_of.size() == n);
+    CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{f, colors.data()}, &L) == MXD_OK);
+    CHECK(L.pass == SecondPass::Color && L.matrix && L.entry_size == sizeof(mxd::ColorRowDev) && L.n == n && (int32_t)L.image_of.size() == n);
     // the routes are those of a plain u8 call: all three kernel families
     CHECK(!L.plans[0].wave && !L.plans[0].band && !L.plans[2].wave && !L.plans[2].band);
     CHECK(L.general.nimgs == 2);
@@ -88,7 +88,7 @@ int main() {
       CHECK(L.descs[k].dst_stride % 16 == 0 && L.descs[k].dst_stride >= imgs[i].crop_w * 3);
       end_max = std::max<size_t>(end_max, off + (size_t)L.descs[k].dst_stride * imgs[i].crop_h);
       // the entry of image i reads what descriptor k writes
-      const mxd::ColorRowDev& r = L.color_rows()[i];
+      const mxd::FmtRowDev& r = L.entry(i);
       CHECK(reinterpret_cast<uintptr_t>(r.src) == off && r.src_stride == L.descs[k].dst_stride);
     }
     CHECK(end_max <= L.scratch_bytes);
@@ -97,15 +97,16 @@ int main() {
     CHECK(L.descs.size() >= L.fmt_at + ((size_t)n * sizeof(mxd::ColorRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
     int32_t blocks = 0;
     for (int32_t i = 0; i < n; i++) {
-      const mxd::ColorRowDev& r = L.color_rows()[i];
+      const mxd::FmtRowDev& r = L.entry(i);
+      const mxd::ColorRowDev& c = reinterpret_cast<const mxd::ColorRowDev&>(r);
       CHECK(r.dst == imgs[i].dst && r.dst_stride == imgs[i].dst_stride);
       CHECK(r.crop_w == imgs[i].crop_w && r.crop_h == imgs[i].crop_h && r.channels == 3);
       for (int k = 0; k < 12; k++) {
         const float want = i == 2 && k == 6 ? 0.0f : (float)(100 * i + k);
-        CHECK(r.m[k] == want);
+        CHECK(c.m[k] == want);
       }
       CHECK(r.blk_begin == blocks);
-      blocks += (imgs[i].crop_h + mxd::kColorRows - 1) / mxd::kColorRows;
+      blocks += (imgs[i].crop_h + mxd::kPixelRows - 1) / mxd::kPixelRows;
     }
     CHECK(L.fmt_blocks == blocks);
     // scratch offsets become addresses for every descriptor and every entry
@@ -115,22 +116,22 @@ int main() {
     L.add_scratch(base);
     for (int32_t k = 0; k < n; k++) {
       CHECK(L.descs[k].dst == base + offs[k]);
-      CHECK(L.color_rows()[L.image_of[k]].src == base + offs[k]);
+      CHECK(L.entry(L.image_of[k]).src == base + offs[k]);
     }
   }
   mxd_set_kernel_policy(MXD_POLICY_AUTO);
   // other matrices, other upload: the cached descriptor slot is keyed by them
   BatchLayout A, B;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &A, colors.data()) == MXD_OK);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, colors.data()}, &A) == MXD_OK);
   colors[4].m[2][3] += 1.0f;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &B, colors.data()) == MXD_OK);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, colors.data()}, &B) == MXD_OK);
   CHECK(A.descs.size() == B.descs.size());
   CHECK(std::memcmp(A.descs.data(), B.descs.data(), A.descs.size() * sizeof(ImgDev)) != 0);
   CHECK(std::memcmp(A.descs.data(), B.descs.data(), A.fmt_at * sizeof(ImgDev)) == 0);
   // without colours the layout is the plain call's
   BatchLayout P;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &P) == MXD_OK);
-  CHECK(!P.colored && P.fmt_count == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{}, &P) == MXD_OK);
+  CHECK(P.pass == SecondPass::None && P.fmt_count == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
   std::printf("ok %d\n", g_checks);
   return 0;
 }

@@ -419,7 +419,7 @@ static void test_layout_formatted(int32_t policy) {
     ranges.push_back({off, size});
     need += size;
     CHECK(rows < L.fmt_count);
-    const mxd::FmtRowDev& e = L.fmt_rows()[rows++];
+    const mxd::FmtRowDev& e = L.entry(rows++);
     CHECK(e.src == d.dst && e.src_stride == d.dst_stride && e.dst == imgs[i].dst && e.dst_stride == imgs[i].dst_stride);
     CHECK(e.crop_w == d.crop_w && e.crop_h == d.crop_h && e.channels == 3 && e.blk_begin == blocks);
     blocks += (d.crop_h + mxd::kFmtRows - 1) / mxd::kFmtRows;
@@ -430,9 +430,9 @@ static void test_layout_formatted(int32_t policy) {
   CHECK(L.descs.size() == L.fmt_at + ((size_t)rows * sizeof(mxd::FmtRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
   // add_scratch turns the offsets into addresses
   uint8_t* const base = reinterpret_cast<uint8_t*>((uintptr_t)1 << 40);
-  const uintptr_t off0 = reinterpret_cast<uintptr_t>(L.fmt_rows()[0].src);
+  const uintptr_t off0 = reinterpret_cast<uintptr_t>(L.entry(0).src);
   L.add_scratch(base);
-  CHECK(L.fmt_rows()[0].src == base + off0);
+  CHECK(L.entry(0).src == base + off0);
   for (int i = 0; i < n; i++) CHECK(L.plans[i].wave ? desc_of[i]->dst == imgs[i].dst : desc_of[i]->dst >= (void*)base);
 }
 

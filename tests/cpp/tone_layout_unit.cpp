@@ -35,6 +35,11 @@ static mxd_image image(int sw, int sh, int rw, int rh, int cx, int cy, int cw, i
   return m;
 }
 
+// Entry j of a tone call's layout (it starts with the head L.entry(j) returns).
+static const mxd::ToneRowDev& tone_entry(BatchLayout& L, int32_t j) {
+  return reinterpret_cast<const mxd::ToneRowDev&>(L.entry(j));
+}
+
 int main() {
   // color_layout_unit.cpp's mixed batch (general, wave, general, Catmull-Rom
   // wave, wave, wave / band) and a seventh image, with all six ops: images 1
@@ -69,9 +74,9 @@ int main() {
     const mxd_color* cols = pass & 4 ? colors.data() : nullptr;
     mxd_set_kernel_policy(prefer_band ? MXD_POLICY_PREFER_BAND : MXD_POLICY_AUTO);
     BatchLayout L;
-    CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, f, &L, cols, tones.data()) == MXD_OK);
-    CHECK(L.toned && !L.colored && L.n == n && (int32_t)L.image_of.size() == n);
-    CHECK(L.tone_matrix == (cols != nullptr));
+    CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{f, cols, tones.data()}, &L) == MXD_OK);
+    CHECK(L.pass == SecondPass::Tone && L.entry_size == sizeof(mxd::ToneRowDev) && L.n == n && (int32_t)L.image_of.size() == n);
+    CHECK(L.matrix == (cols != nullptr));
     // the routes are those of a plain u8 call
     CHECK(!L.plans[0].wave && !L.plans[0].band && !L.plans[2].wave && !L.plans[2].band);
     if (!prefer_band) CHECK(L.plans[1].wave && L.plans[3].wave && L.plans[3].s == 4 && L.plans[4].wave && L.bands.empty());
@@ -85,7 +90,7 @@ int main() {
       CHECK(off % 256 == 0 && off < L.tone_ws_at);
       CHECK(L.descs[k].dst_stride % 16 == 0 && L.descs[k].dst_stride >= imgs[i].crop_w * 3);
       end_max = std::max<size_t>(end_max, off + (size_t)L.descs[k].dst_stride * imgs[i].crop_h);
-      const mxd::ToneRowDev& r = L.tone_rows()[i];
+      const mxd::FmtRowDev& r = L.entry(i);
       CHECK(reinterpret_cast<uintptr_t>(r.src) == off && r.src_stride == L.descs[k].dst_stride);
     }
     CHECK(end_max <= L.tone_ws_at && L.tone_ws_at % 256 == 0);
@@ -96,12 +101,14 @@ int main() {
     CHECK(L.descs.size() >= L.fmt_at + ((size_t)n * sizeof(mxd::ToneRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
     int32_t blocks = 0, hist = 0, nstat = 0;
     for (int32_t i = 0; i < n; i++) {
-      const mxd::ToneRowDev& r = L.tone_rows()[i];
-      CHECK(r.dst == imgs[i].dst && r.dst_stride == imgs[i].dst_stride);
-      CHECK(r.crop_w == imgs[i].crop_w && r.crop_h == imgs[i].crop_h && r.channels == 3);
+      const mxd::ToneRowDev& r = tone_entry(L, i);
+      const mxd::FmtRowDev& h = r.color.head;
+      CHECK(&h == &L.entry(i));
+      CHECK(h.dst == imgs[i].dst && h.dst_stride == imgs[i].dst_stride);
+      CHECK(h.crop_w == imgs[i].crop_w && h.crop_h == imgs[i].crop_h && h.channels == 3);
       CHECK(r.op == tones[i].op && r.arg == tones[i].arg && r.factor == tones[i].factor);
-      for (int k = 0; k < 12; k++) CHECK(r.m[k] == (cols ? (float)(100 * i + k) : k % 5 == 0 ? 1.0f : 0.0f));
-      CHECK(r.blk_begin == blocks && r.hist_begin == hist);
+      for (int k = 0; k < 12; k++) CHECK(r.color.m[k] == (cols ? (float)(100 * i + k) : k % 5 == 0 ? 1.0f : 0.0f));
+      CHECK(h.blk_begin == blocks && r.hist_begin == hist);
       CHECK(mxd::tone_needs_stats(r.op) == stats[i]);
       if (stats[i]) {
         CHECK(r.stat_off == (int32_t)(nstat * stat_block));
@@ -112,16 +119,16 @@ int main() {
       }
       CHECK(r.lut_off == (int32_t)(L.tone_stat_bytes + (size_t)i * mxd::kToneLutBytes) && r.lut_off % 256 == 0);
       CHECK((size_t)r.lut_off + mxd::kToneLutBytes <= L.scratch_bytes - L.tone_ws_at);
-      blocks += (imgs[i].crop_h + mxd::kColorRows - 1) / mxd::kColorRows;
+      blocks += (imgs[i].crop_h + mxd::kPixelRows - 1) / mxd::kPixelRows;
     }
     CHECK(L.fmt_blocks == blocks && L.tone_hist_blocks == hist && hist > 0);
     // tone_hist's search (the last image whose hist_begin <= block) finds an image with statistics
     for (int32_t blk = 0; blk < hist; blk++) {
       int32_t found = 0;
       for (int32_t i = 0; i < n; i++)
-        if (L.tone_rows()[i].hist_begin <= blk) found = i;
+        if (tone_entry(L, i).hist_begin <= blk) found = i;
       CHECK(stats[found]);
-      const int32_t y0 = (blk - L.tone_rows()[found].hist_begin) * mxd::kToneHistRows;
+      const int32_t y0 = (blk - tone_entry(L, found).hist_begin) * mxd::kToneHistRows;
       CHECK(y0 >= 0 && y0 < imgs[found].crop_h);
     }
     // scratch offsets become addresses for every descriptor and entry, and the workspace gets its own
@@ -131,7 +138,7 @@ int main() {
     L.add_scratch(base);
     for (int32_t k = 0; k < n; k++) {
       CHECK(L.descs[k].dst == base + offs[k]);
-      CHECK(L.tone_rows()[L.image_of[k]].src == base + offs[k]);
+      CHECK(L.entry(L.image_of[k]).src == base + offs[k]);
     }
     CHECK(L.tone_ws == base + L.tone_ws_at);
   }
@@ -141,19 +148,19 @@ int main() {
     std::vector<mxd_tone> flat(n, mxd_tone{MXD_TONE_POSTERIZE, 4, 0.0f, 0});
     flat[2].op = MXD_TONE_NONE;
     BatchLayout L;
-    CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &L, nullptr, flat.data()) == MXD_OK);
+    CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, nullptr, flat.data()}, &L) == MXD_OK);
     CHECK(L.tone_hist_blocks == 0 && L.tone_stat_bytes == 0 && L.fmt_blocks > 0);
-    for (int32_t i = 0; i < n; i++) CHECK(L.tone_rows()[i].stat_off == -1 && L.tone_rows()[i].hist_begin == 0);
+    for (int32_t i = 0; i < n; i++) CHECK(tone_entry(L, i).stat_off == -1 && tone_entry(L, i).hist_begin == 0);
   }
   // other ops or parameters, other upload: the cached descriptor slot is keyed by them
   BatchLayout A, B, C, D;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &A, nullptr, tones.data()) == MXD_OK);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, nullptr, tones.data()}, &A) == MXD_OK);
   tones[5].factor = 0.75f;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &B, nullptr, tones.data()) == MXD_OK);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, nullptr, tones.data()}, &B) == MXD_OK);
   tones[3].arg = 4;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &C, nullptr, tones.data()) == MXD_OK);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, nullptr, tones.data()}, &C) == MXD_OK);
   tones[6].op = MXD_TONE_NONE;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &D, nullptr, tones.data()) == MXD_OK);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, nullptr, tones.data()}, &D) == MXD_OK);
   const BatchLayout* all[4] = {&A, &B, &C, &D};
   for (int a = 0; a < 4; a++)
     for (int b = a + 1; b < 4; b++) {
@@ -163,10 +170,10 @@ int main() {
     }
   // without tones the layouts are the colour call's and the plain call's
   BatchLayout K, P;
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &K, colors.data()) == MXD_OK);
-  CHECK(K.colored && !K.toned && K.tone_stat_bytes == 0 && K.tone_ws_at == 0 && K.fmt_count == n);
-  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, nullptr, &P) == MXD_OK);
-  CHECK(!P.colored && !P.toned && P.fmt_count == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, colors.data()}, &K) == MXD_OK);
+  CHECK(K.pass == SecondPass::Color && K.tone_stat_bytes == 0 && K.tone_ws_at == 0 && K.fmt_count == n);
+  CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{}, &P) == MXD_OK);
+  CHECK(P.pass == SecondPass::None && P.fmt_count == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
   std::printf("ok %d\n", g_checks);
   return 0;
 }

@@ -77,7 +77,7 @@ def _check(src, plain, tones, mode, tag, mats=None, **kw):
 def windows():
     """Crop windows 5x7, 31x29 (w mod 4 != 0, rows that are no 16-byte
     multiple), 64x8 (one row group of every kernel) and 70x41 (three tone_hist
-    workgroups add into one statistics block, six tone_rows workgroups), the
+    workgroups add into one statistics block, six pixel_rows workgroups), the
     second mirrored."""
     imgs = [synth(61, 97, 3, 700 + k) for k in range(4)]
     geoms = [(40, 36, 3, 5, 5, 7, 0), (40, 36, 1, 3, 31, 29, 1), (80, 50, 9, 11, 64, 8, 0), (90, 60, 7, 2, 70, 41, 0)]
@@ -107,11 +107,13 @@ def test_every_op_in_u8(windows, tone):
 @pytest.mark.parametrize("tone", [SIX[4], SIX[5]], ids=["equalize", "contrast"])
 def test_every_output_form_with_destinations_that_force_element_stores(windows, tone, mode):
     """Bases one element past a 256-byte boundary, padded rows and planes, and
-    a matrix per image behind the table."""
+    a matrix per image behind the table; the same destinations without a
+    matrix (the kernel that skips the map, on its element stores)."""
     src, plain = windows
     mats = C.eight_matrices()[1:5]
     _check(src, plain, [tone] * 4, mode, "odd", mats, dst_pad=2, plane_pad=2, dst_shift=1)
     _check(src, plain, [tone] * 4, mode, "aligned")
+    _check(src, plain, [tone] * 4, mode, "odd, no matrix", None, dst_pad=2, plane_pad=2, dst_shift=1)
 
 
 def test_one_image(windows):

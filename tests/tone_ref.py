@@ -1,7 +1,7 @@
 """NumPy restatement of the tone operations' arithmetic (DESIGN.md section 2;
 include/mxd_amd.h, mxd_tone): the 3 x 256 byte table of an operation for the
 RGB pixels it is given, and the pixels looked up in it.  Shares nothing with
-csrc/tone.cpp or csrc/tone_rows.hip.  The arithmetic is Pillow's, so
+csrc/tone.cpp or csrc/row_stage.hip.  The arithmetic is Pillow's, so
 pillow_apply() -- the calls timm's and torchvision's PIL policies make -- is
 the independent yardstick the tests hold both against."""
 import numpy as np
