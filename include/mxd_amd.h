@@ -62,11 +62,17 @@ extern "C" {
  * 7, added without a new number (test for MXD_HAS_TONE / the symbols): the
  * per-image tone operations -- mxd_tone_op, mxd_tone, mxd_tone_table_u8,
  * mxd_tone_apply_u8, mxd_resize_crop_batch_tone,
- * mxd_resize_crop_to_device_tone, mxd_jpeg_resize_crop_to_device_tone. */
+ * mxd_resize_crop_to_device_tone, mxd_jpeg_resize_crop_to_device_tone.
+ * 7, added without a new number (test for MXD_HAS_WARP / the symbols): the
+ * per-image affine warps -- mxd_warp_mode, mxd_warp, mxd_warp_validate,
+ * mxd_warp_apply_u8,
+ * mxd_resize_crop_batch_warp, mxd_resize_crop_to_device_warp,
+ * mxd_jpeg_resize_crop_to_device_warp. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
 #define MXD_HAS_TONE 1
+#define MXD_HAS_WARP 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -632,6 +638,76 @@ int mxd_resize_crop_to_device_tone(const mxd_image* images, const mxd_tone* tone
                                    int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
 int mxd_jpeg_resize_crop_to_device_tone(const mxd_jpeg_image* images, const mxd_tone* tones, const mxd_color* colors,
                                         int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
+
+/* ---- per-image affine warps (ABI 7 additions; feature test: MXD_HAS_WARP)
+ *
+ * A warp acts on the u8 RGB result of an image's geometry -- crop_w x crop_h,
+ * exactly what MXD_U8 gives -- and produces a u8 RGB image of the same size:
+ * Pillow's Image.transform(size, AFFINE, m, resample, fillcolor=fill), bit
+ * for bit.  m[0..5] maps an output pixel to a source position, in pixels;
+ * every output pixel no rule below writes gets fill[0..2] (fill[3] is not
+ * read).  With FLOOR(v) = v < 0 ? (int)floor(v) : (int)v and
+ * COORD(v) = v < 0 ? -1 : (int)v:
+ *
+ *   NEAREST, m[1] == 0 and m[3] == 0 (a translate or scale): index tables by
+ *     sequential accumulation in double: xo = m[2] + m[0] * 0.5; for x = 0 ..
+ *     w - 1 in order xt[x] = COORD(xo), xo += m[0]; yt[y] likewise from
+ *     m[5] + m[4] * 0.5 and m[4]; out[y][x] = src[yt[y]][xt[x]] where both
+ *     are in range.
+ *   NEAREST otherwise: 16.16 fixed point, FIX(v) = FLOOR(v * 65536.0 + 0.5);
+ *     A0, A1, A3, A4 = FIX(m[0]), ...; A2 = FIX(m[2] + m[0] * 0.5 + m[1] * 0.5),
+ *     A5 = FIX(m[5] + m[3] * 0.5 + m[4] * 0.5); in 64-bit integers with an
+ *     arithmetic shift xin = (A2 + A1 y + A0 x) >> 16,
+ *     yin = (A5 + A4 y + A3 x) >> 16; src[yin][xin] where both are in range.
+ *   BILINEAR: in double, every operation rounded, none fused, left to right:
+ *     sx = m[0] (x + 0.5) + m[1] (y + 0.5) + m[2], sy likewise from m[3..5];
+ *     not written if sx < 0, sx >= w, sy < 0 or sy >= h; else sx -= 0.5,
+ *     sy -= 0.5, X = FLOOR(sx), Y = FLOOR(sy), dx = sx - X, dy = sy - Y,
+ *     x0 = clamp(X, 0, w - 1), x1 = clamp(X + 1, 0, w - 1),
+ *     yc = clamp(Y, 0, h - 1); per channel v1 = p[x0] + (p[x1] - p[x0]) dx on
+ *     row yc, v2 the same on row Y + 1 if 0 <= Y + 1 < h, else v1; the result
+ *     is (uint8) trunc(v1 + (v2 - v1) dy): truncation, where the rest of this
+ *     library rounds.
+ *
+ * In a call the stage order is geometry, warp, tone, colour, output form: the
+ * tone statistics are those of the warped result, fill pixels included. */
+enum mxd_warp_mode { MXD_WARP_NONE = 0, MXD_WARP_NEAREST = 1, MXD_WARP_BILINEAR = 2 };
+
+typedef struct mxd_warp {
+  int32_t mode;    /* mxd_warp_mode; NONE: the image's bytes stay as they are, nothing else is read */
+  uint8_t fill[4]; /* r, g, b; fill[3] is not read */
+  double m[6];     /* Pillow's AFFINE data */
+} mxd_warp;
+
+/* Host only: the CPU statement of the arithmetic above on the w x h packed
+ * RGB pixels at rgb (rows stride bytes apart) into out (rows out_stride bytes
+ * apart; may overlap rgb).  MXD_ERR_INVALID for a bad warp (as the calls
+ * below). */
+int mxd_warp_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, int64_t stride, const mxd_warp* warp, uint8_t* out,
+                      int64_t out_stride);
+/* Host only: the checks the calls below make of warp for a w x h crop window
+ * (MXD_OK, or MXD_ERR_INVALID with their message). */
+int mxd_warp_validate(const mxd_warp* warp, int32_t w, int32_t h);
+
+/* The _tone calls with warps[i] applied to images[i]'s result before
+ * tones[i].  tones, colors and fmt may each be NULL.  Device destinations
+ * only.  MXD_ERR_INVALID (the message names the image) for a null warps, an
+ * unknown mode, a non-finite entry, channels != 3, or a matrix that maps one
+ * of the corners (0, 0), (w, 0), (0, h), (w, h) of the crop window to a source
+ * coordinate of magnitude >= 32768; everything is validated before any
+ * launch.  Every image is resized as a u8 image into a scratch by the kernels
+ * of the plain calls; one more launch on the same stream (two when some
+ * image takes the table path) warps them, into the destinations when nothing
+ * follows, else into a second scratch the row stage of the _tone calls reads. */
+int mxd_resize_crop_batch_warp(const mxd_image* images, const mxd_warp* warps, const mxd_tone* tones,
+                               const mxd_color* colors, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                               int32_t device, void* stream);
+int mxd_resize_crop_to_device_warp(const mxd_image* images, const mxd_warp* warps, const mxd_tone* tones,
+                                   const mxd_color* colors, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                                   int32_t device);
+int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_warp* warps, const mxd_tone* tones,
+                                        const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                        const mxd_out_format* fmt, int32_t device);
 
 /* Diagnostics: where a host-side pipeline's time goes, summed over every
  * thread since the last reset (reset != 0 zeroes them after reading).

@@ -429,6 +429,14 @@ int launch_second_pass(const BatchLayout& L, const ImgDev* dev, const mxd::OutFm
   return MXD_OK;
 }
 
+// The warp stage of a warp call: between the resize kernels and the second pass.
+int launch_warp_stage(const BatchLayout& L, const ImgDev* dev, void* stream) {
+  if (mxd::launch_warp(reinterpret_cast<const mxd::WarpRowDev*>(dev + L.warp_at), L.n, L.warp_tiles, L.warp_tab_count,
+                       L.warp_tab, stream))
+    return fail(MXD_ERR_DEVICE, std::string("warp launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return MXD_OK;
+}
+
 // One launchable batch: its layout, the upload, the launches.
 int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
                    const Stored* stored, const PostOps& ops) {
@@ -447,6 +455,7 @@ int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_
   int launch_rc = launch_all(L, dev, ws, ops.resize_formats() ? &ofd : nullptr, stream);
   // The second pass, behind the joins: every resize kernel that wrote scratch
   // rows is ordered before it on the caller's stream.
+  if (launch_rc == MXD_OK && L.warped) launch_rc = launch_warp_stage(L, dev, stream);
   if (launch_rc == MXD_OK) launch_rc = launch_second_pass(L, dev, ofd, stream);
   // The batch is counted on a failed launch too (see launch_all).
   const int rel = release_descs(ws, stream, hit);
@@ -458,6 +467,8 @@ int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_
 int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* out_dtype, mxd_out_format* f32_fmt) {
   if (!ops->per_image()) return MXD_OK;
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
+  if (ops->warps)
+    if (int rc = warp_validate(images, ops->warps, n)) return rc;
   if (ops->tones)
     if (int rc = tone_validate(images, ops->tones, n)) return rc;
   if (ops->colors)

@@ -344,6 +344,69 @@ mxd::FmtRowDev entry_head(const mxd_image& im, const mxd_image& caller, int32_t 
                         im.crop_w, im.crop_h, im.channels, blk_begin};
 }
 
+// Whether a warp takes the table path: Pillow's scale path of NEAREST.
+bool warp_tabled(const mxd_warp& w) { return w.mode == MXD_WARP_NEAREST && w.m[1] == 0.0 && w.m[3] == 0.0; }
+
+// A warp call's scratch behind the rows A the resize kernels write: rows B
+// when a second pass follows the warp stage, then the index tables.
+void place_warp_scratch(Batch& b, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  if (L.pass != SecondPass::None) {
+    L.warp_b_at = (L.scratch_bytes + 255) & ~(size_t)255;
+    L.scratch_bytes = L.warp_b_at + L.scratch_bytes;
+  }
+  L.warp_tab_at = (L.scratch_bytes + 255) & ~(size_t)255;
+  size_t tab_bytes = 0;
+  for (int32_t i = 0; i < b.n; i++)
+    if (warp_tabled(ops.warps[i])) {
+      L.warp_tab_count++;
+      tab_bytes += (((size_t)L.images[i].crop_w + L.images[i].crop_h) * 4 + 15) & ~(size_t)15;
+    }
+  if (tab_bytes > 0) L.scratch_bytes = L.warp_tab_at + tab_bytes;
+}
+
+// The warp stage's entries, in batch order, behind everything else of the
+// upload: modes, fills and matrices are part of its bytes, so a cached slot is
+// reused only for the same ones.
+void append_warps(Batch& b, const mxd_image* callers, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  L.warp_at = L.descs.size();
+  L.descs.resize(L.warp_at + ((size_t)b.n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
+  size_t tab_at = L.warp_tab_at;
+  int32_t tabs = 0;
+  for (int32_t i = 0; i < b.n; i++) {
+    const mxd_image& im = L.images[i];
+    const mxd_warp& wp = ops.warps[i];
+    mxd::WarpRowDev& e = L.warp_entry(i);
+    e.src = static_cast<const uint8_t*>(im.dst);
+    e.src_stride = im.dst_stride;
+    if (L.pass != SecondPass::None) {
+      e.dst = static_cast<uint8_t*>(im.dst) + L.warp_b_at;
+      e.dst_stride = im.dst_stride;
+    } else {
+      e.dst = static_cast<uint8_t*>(callers[i].dst);
+      e.dst_stride = callers[i].dst_stride;
+    }
+    e.w = im.crop_w, e.h = im.crop_h;
+    e.tile_begin = L.warp_tiles;
+    e.tiles_x = (im.crop_w + mxd::kWarpTileW - 1) / mxd::kWarpTileW;
+    L.warp_tiles += e.tiles_x * ((im.crop_h + mxd::kWarpTileH - 1) / mxd::kWarpTileH);
+    e.path = wp.mode == MXD_WARP_NONE       ? mxd::kWarpCopy
+             : warp_tabled(wp)              ? mxd::kWarpTable
+             : wp.mode == MXD_WARP_NEAREST  ? mxd::kWarpFixed
+                                            : mxd::kWarpBilinear;
+    e.fill = (uint32_t)wp.fill[0] | (uint32_t)wp.fill[1] << 8 | (uint32_t)wp.fill[2] << 16;
+    e.tab_off = 0, e.tab_index = -1;
+    if (e.path == mxd::kWarpTable) {
+      e.tab_off = (int32_t)(tab_at - L.warp_tab_at);
+      e.tab_index = tabs++;
+      tab_at += (((size_t)im.crop_w + im.crop_h) * 4 + 15) & ~(size_t)15;
+    }
+    // (MXD_WARP_NONE reads nothing of the matrix: zeros, so equal calls make equal bytes)
+    for (int k = 0; k < 6; k++) e.m[k] = e.path == mxd::kWarpCopy ? 0.0 : wp.m[k];
+  }
+}
+
 // After every descriptor, in ImgDev-sized blocks: the unit -> image tables of
 // the band launches whose images differ in unit count (int32 each), then the
 // second pass's entries: part of the upload's bytes, so a cached slot is
@@ -366,6 +429,7 @@ void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
   if (!unit_tables.empty())
     std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.tables_at), unit_tables.data(), unit_tables.size() * 4);
   L.fmt_at = L.descs.size();
+  if (L.warped) place_warp_scratch(b, ops);
   if (L.pass == SecondPass::None) return;
   for (int32_t i = 0; i < b.n; i++) L.fmt_count += second_pass_reads(b, i) ? 1 : 0;
   L.descs.resize(L.fmt_at + ((size_t)L.fmt_count * L.entry_size + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
@@ -376,6 +440,7 @@ void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
     const mxd_image& im = L.images[i];
     mxd::FmtRowDev& head = L.entry(j++);
     head = entry_head(im, callers[i], L.fmt_blocks);
+    head.src += L.warp_b_at;  // (a warp call: the warp stage's rows)
     L.fmt_blocks += (im.crop_h + block_rows - 1) / block_rows;
     if (L.pass == SecondPass::Format) continue;
     mxd::ColorRowDev& c = reinterpret_cast<mxd::ColorRowDev&>(head);
@@ -412,6 +477,14 @@ void BatchLayout::add_scratch(uint8_t* base) {
     if (pass != SecondPass::Format || !plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
   for (int32_t j = 0; j < fmt_count; j++) entry(j).src = base + reinterpret_cast<uintptr_t>(entry(j).src);
   if (pass == SecondPass::Tone) tone_ws = base + tone_ws_at;
+  if (warped) {
+    for (int32_t i = 0; i < n; i++) {
+      mxd::WarpRowDev& e = warp_entry(i);
+      e.src = base + reinterpret_cast<uintptr_t>(e.src);
+      if (pass != SecondPass::None) e.dst = base + reinterpret_cast<uintptr_t>(e.dst);
+    }
+    warp_tab = base + warp_tab_at;
+  }
 }
 
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
@@ -425,6 +498,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
                  : L.pass == SecondPass::Format ? sizeof(mxd::FmtRowDev)
                                                 : 0;
   L.matrix = ops.colors != nullptr;
+  L.warped = ops.warps != nullptr;
   // A formatted call plans its kernels as a u8 call does: the wave kernels
   // exist in the same shapes in every output mode and write any element
   // alignment, and an image they do not take is resized into u8 scratch rows
@@ -453,6 +527,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = wave_groups(b)) return rc;
   if (int rc = general_group(b)) return rc;
   append_tables(b, callers, ops);
+  if (L.warped) append_warps(b, callers, ops);
   // Largest first (a band unit is a workgroup, ~4 wave units).
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});

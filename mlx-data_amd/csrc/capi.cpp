@@ -174,6 +174,16 @@ static int post_ops(const mxd_out_format* fmt, const mxd_color* colors, const mx
   return MXD_OK;
 }
 
+// The head of the _warp entry points: warps required, everything else optional.
+static int warp_ops(const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones, const mxd_warp* warps,
+                    int32_t n, PostOps* ops) {
+  if (fmt)
+    if (int rc = fmt_validate(fmt, 0)) return rc;
+  if (n > 0 && !warps) return fail(MXD_ERR_INVALID, "mxd: null warps");
+  *ops = n > 0 ? PostOps{fmt, colors, tones, warps} : PostOps{fmt};
+  return MXD_OK;
+}
+
 extern "C" {
 
 int mxd_abi_version(void) { return MXD_ABI_VERSION; }
@@ -275,6 +285,14 @@ int mxd_resize_crop_batch_tone(const mxd_image* images, const mxd_tone* tones, c
                                int32_t out_dtype, const mxd_out_format* fmt, int32_t device, void* stream) {
   PostOps ops;
   if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
+}
+
+int mxd_resize_crop_batch_warp(const mxd_image* images, const mxd_warp* warps, const mxd_tone* tones,
+                               const mxd_color* colors, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                               int32_t device, void* stream) {
+  PostOps ops;
+  if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
   return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
@@ -482,6 +500,14 @@ int mxd_resize_crop_to_device_tone(const mxd_image* images, const mxd_tone* tone
   return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
+int mxd_resize_crop_to_device_warp(const mxd_image* images, const mxd_warp* warps, const mxd_tone* tones,
+                                   const mxd_color* colors, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                                   int32_t device) {
+  PostOps ops;
+  if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
+  return host_path(images, n, out_dtype, device, true, nullptr, ops);
+}
+
 int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device) {
   if (int rc = fmt_validate(fmt, 0)) return rc;
   return host_path(images, n, MXD_U8, device, true, nullptr, PostOps{fmt});
@@ -589,6 +615,14 @@ int mxd_jpeg_resize_crop_to_device_tone(const mxd_jpeg_image* images, const mxd_
                                         int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
   if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  return jpeg_path(images, n, out_dtype, device, true, ops);
+}
+
+int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_warp* warps, const mxd_tone* tones,
+                                        const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                        const mxd_out_format* fmt, int32_t device) {
+  PostOps ops;
+  if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
   return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 

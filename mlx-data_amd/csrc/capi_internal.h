@@ -265,22 +265,31 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
 // What follows the resize of a call, as every layer below the entry points
 // passes it on.  fmt: a formatted output (mxd_out_format).  colors: a colour
 // call, colors[i] belongs to images[i].  tones: a tone call, tones[i] belongs
-// to images[i]; colors may be null then (no matrix).
+// to images[i]; colors may be null then (no matrix).  warps: a warp call,
+// warps[i] belongs to images[i]; every other member may be null then.
 // The second pass (row_stage.hip) such a call launches behind its resize
 // kernels: format_rows for the images of a formatted call that no wave kernel
-// takes, pixel_rows for every image of a colour or tone call.
+// takes, pixel_rows for every image of a colour or tone call.  A warp call
+// resizes every image into scratch rows A in u8 and runs the warp stage
+// (warp.hip) in front of the second pass, which then reads every image (a
+// format alone: through pixel_rows with identity matrices) from the warp's
+// scratch rows B; with no second pass the warp stage writes the u8
+// destinations itself.
 enum class SecondPass : int32_t { None, Format, Color, Tone };
 struct PostOps {
   const mxd_out_format* fmt = nullptr;
   const mxd_color* colors = nullptr;
   const mxd_tone* tones = nullptr;
+  const mxd_warp* warps = nullptr;
   // (a format alone, or nullptr, converts: a formatted / plain call)
-  PostOps(const mxd_out_format* f = nullptr, const mxd_color* c = nullptr, const mxd_tone* t = nullptr)
-      : fmt(f), colors(c), tones(t) {}
-  bool any() const { return fmt || colors || tones; }
-  bool per_image() const { return colors || tones; }  // a colour or tone call
+  PostOps(const mxd_out_format* f = nullptr, const mxd_color* c = nullptr, const mxd_tone* t = nullptr,
+          const mxd_warp* w = nullptr)
+      : fmt(f), colors(c), tones(t), warps(w) {}
+  bool any() const { return fmt || colors || tones || warps; }
+  bool per_image() const { return colors || tones || warps; }  // a colour, tone or warp call
   SecondPass pass() const {
-    return tones ? SecondPass::Tone : colors ? SecondPass::Color : fmt ? SecondPass::Format : SecondPass::None;
+    // (a warp call with a format alone: pixel_rows with the identity, which is exact)
+    return tones ? SecondPass::Tone : colors || (warps && fmt) ? SecondPass::Color : fmt ? SecondPass::Format : SecondPass::None;
   }
   // The resize kernels write the format themselves (wave kernels in their
   // formatted mode).  A colour or tone call's run in their u8 mode into
@@ -288,7 +297,8 @@ struct PostOps {
   bool resize_formats() const { return pass() == SecondPass::Format; }
   // The call's share for the images from `first` on (a host-path chunk).
   PostOps at(int32_t first) const {
-    return PostOps{fmt, colors ? colors + first : nullptr, tones ? tones + first : nullptr};
+    return PostOps{fmt, colors ? colors + first : nullptr, tones ? tones + first : nullptr,
+                   warps ? warps + first : nullptr};
   }
 };
 
@@ -344,6 +354,19 @@ struct BatchLayout {
   size_t tone_ws_at = 0, tone_stat_bytes = 0;
   int32_t tone_hist_blocks = 0;
   uint8_t* tone_ws = nullptr;
+  // Warp call only.  After the second pass's entries, from warp_at, one
+  // WarpRowDev per image in batch order (warp_tiles workgroups).  Their src
+  // are the scratch rows A the resize kernels write.  With a second pass
+  // their dst (and the second pass's src) are scratch rows B, the same rows
+  // warp_b_at (a multiple of 256) further on; else the caller's destinations
+  // and warp_b_at == 0.  The index tables of the images that take the table
+  // path (warp_tab_count of them, w + h int32 each) lie from warp_tab_at,
+  // behind B and before the tone workspace; all counted in scratch_bytes.
+  bool warped = false;
+  size_t warp_at = 0, warp_b_at = 0, warp_tab_at = 0;
+  int32_t warp_tiles = 0, warp_tab_count = 0;
+  uint8_t* warp_tab = nullptr;
+  mxd::WarpRowDev& warp_entry(int32_t i) { return reinterpret_cast<mxd::WarpRowDev*>(descs.data() + warp_at)[i]; }
   const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
   void add_scratch(uint8_t* base);
 };
@@ -388,7 +411,7 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
               const Stored* stored = nullptr, PostOps ops = {});
 // The head of every colour and tone call (nothing to do for the others):
-// validates the tones, then the matrices, makes ops->fmt the format pixel_rows
+// validates the warps, the tones, then the matrices, makes ops->fmt the format pixel_rows
 // writes (f32_fmt, the q / 255 table, for MXD_F32_DIV255; null stays null for
 // MXD_U8) and *out_dtype the form the kernels are planned in.
 int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* out_dtype, mxd_out_format* f32_fmt);
@@ -404,6 +427,13 @@ int color_validate(const mxd_image* images, const mxd_color* colors, int32_t n);
 // Tone operations (tone.cpp).
 // tones[i] against images[i] (images may be null: the tones alone).
 int tone_validate(const mxd_image* images, const mxd_tone* tones, int32_t n);
+
+// ---------------------------------------------------------------------------
+// Affine warps (warp.cpp).
+// warps[i] against images[i] (its crop window's size).
+int warp_validate(const mxd_image* images, const mxd_warp* warps, int32_t n);
+// One warp against a w x h image.
+int warp_validate_one(const mxd_warp& warp, int32_t w, int32_t h);
 
 // ---------------------------------------------------------------------------
 // Formatted outputs (outfmt.cpp).

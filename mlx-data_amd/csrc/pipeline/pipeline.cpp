@@ -263,7 +263,8 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
   std::vector<std::shared_ptr<const JpegSource>> keep;  // alive for the call
   std::vector<mxd_color> pc, jc;  // the colours of `plain` and `jp`, image for image
   std::vector<mxd_tone> pt, jt;   // and their tones
-  bool colored = false, toned = false;
+  std::vector<mxd_warp> pw, jw;   // and their warps
+  bool colored = false, toned = false, warped = false;
   for (size_t i = 0; i < n; i++) {
     const Job& j = jobs[i];
     mxd_color c;
@@ -272,18 +273,44 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
     mxd_tone t{};  // (MXD_TONE_NONE for a plan without a tone op)
     if (j.plan.toned) t.op = j.plan.tone_op, t.arg = j.plan.tone_arg, t.factor = j.plan.tone_factor;
     toned = toned || j.plan.toned;
+    mxd_warp w{};  // (MXD_WARP_NONE for a plan without a warp)
+    if (j.plan.warped) {
+      w.mode = j.plan.warp_mode;
+      std::memcpy(w.fill, j.plan.warp_fill.data(), sizeof w.fill);
+      std::memcpy(w.m, j.plan.warp_m.data(), sizeof w.m);
+    }
+    warped = warped || j.plan.warped;
     if (auto src = j.plan.src->jpeg()) {
       jp.push_back(jpeg_desc(j.plan, *src, j.dst, j.stride));
       jc.push_back(c);
       jt.push_back(t);
+      jw.push_back(w);
       keep.push_back(std::move(src));
     } else {
       plain.push_back(plan_desc(j.plan, j.dst, j.stride));
       pc.push_back(c);
       pt.push_back(t);
+      pw.push_back(w);
     }
   }
   g_run_jpeg.fetch_add((int64_t)jp.size());
+  // Some plan is warped: the whole launch goes through the _warp calls, plans
+  // without a warp with MXD_WARP_NONE; tones and matrices only if some plan
+  // has them.  Device destinations only.
+  if (warped) {
+    if (!dst_device) throw std::logic_error("mxd: a warp launch needs device destinations");
+    mxd_out_format of{};
+    if (fmt) of = abi_format(*fmt, jobs[0]);
+    if (!jp.empty())
+      if (int rc = mxd_jpeg_resize_crop_to_device_warp(jp.data(), jw.data(), toned ? jt.data() : nullptr,
+                                                       colored ? jc.data() : nullptr, (int32_t)jp.size(), dtype,
+                                                       fmt ? &of : nullptr, device))
+        return rc;
+    if (plain.empty()) return MXD_OK;
+    return mxd_resize_crop_to_device_warp(plain.data(), pw.data(), toned ? pt.data() : nullptr,
+                                          colored ? pc.data() : nullptr, (int32_t)plain.size(), dtype,
+                                          fmt ? &of : nullptr, device);
+  }
   // Some plan is toned: the whole launch goes through the _tone calls, plans
   // without a tone op with MXD_TONE_NONE; no matrices unless some plan is
   // coloured (then the others get the identity).  Device destinations only.
@@ -491,8 +518,8 @@ void run_host(const std::vector<Job>& jobs, int32_t dtype, const OutFormat* fmt 
   const std::vector<Slice> sl = split_batch((int64_t)n, (int64_t)devs.size(), g_rr.fetch_add(k));
   // a coloured plan anywhere: every slice takes the device call and one copy
   // back, like a formatted batch (each slice carries its own jobs' matrices)
-  bool colored = false;  // (or toned: device calls only, too)
-  for (const Job& j : jobs) colored = colored || j.plan.colored || j.plan.toned;
+  bool colored = false;  // (or toned, or warped: device calls only, too)
+  for (const Job& j : jobs) colored = colored || j.plan.colored || j.plan.toned || j.plan.warped;
   auto slice = [&jobs, dtype, &devs, &sl, fmt, colored](size_t s) -> std::string {
     const Job* first = jobs.data() + sl[s].begin;
     const size_t count = (size_t)(sl[s].end - sl[s].begin);
@@ -682,12 +709,23 @@ void verify_dimensions(int64_t w, int64_t h, int64_t c) {
   if (c <= 0 || c > 4) throw std::runtime_error("image: channels must be 0 < c <= 4");
 }
 
+// The plan a geometric op (crop, flip, resize) goes on from: a pending warp
+// runs first, the op then works on its bytes.
+ImagePlan geometry_view(const std::shared_ptr<Array>& img) {
+  ImagePlan p = view(img);
+  if (p.warped) {
+    img->data();
+    p = view(img);
+  }
+  return p;
+}
+
 std::shared_ptr<Array> make(const ImagePlan& p) { return std::make_shared<Array>(std::make_shared<const ImagePlan>(p)); }
 
 // core::image::resize (core/image/ImageTransform.cpp:41-62).
 std::shared_ptr<Array> plan_resize(const std::shared_ptr<Array>& img, int64_t dw, int64_t dh, int filter) {
   verify_dimensions(dw, dh, img->shape(2));
-  ImagePlan p = view(img);
+  ImagePlan p = geometry_view(img);
   // (an alpha-weighted same-size resize is not the identity: it zeroes the
   // colour of transparent pixels, so it runs before the next one)
   const bool identity_so_far =
@@ -731,7 +769,7 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
     for (int64_t r = 0; r < h; r++) std::memcpy(d + r * w * c * isz, s + ((y + r) * W + x) * c * isz, w * c * isz);
     return out;
   }
-  ImagePlan p = view(img);
+  ImagePlan p = geometry_view(img);
   if (p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) {
     // the op's statistics are those of the window it saw: run it, crop its bytes
     img->data();
@@ -867,7 +905,7 @@ std::shared_ptr<Array> ImageRandomHFlip::apply_video(const std::shared_ptr<Array
   for (int64_t i = 0; i < video->shape(0); i++) {
     auto f = video_frame(video, i);
     verify_dimensions(f->shape(1), f->shape(0), f->shape(2));
-    ImagePlan p = view(f);
+    ImagePlan p = geometry_view(f);
     p.flip = !p.flip;
     frames.push_back(make(p));
   }
@@ -880,7 +918,7 @@ std::shared_ptr<Array> ImageRandomHFlip::apply_image(const std::shared_ptr<Array
   auto st = get_state();
   if (u(st->gen) <= prob_) {
     verify_dimensions(img->shape(1), img->shape(0), img->shape(2));
-    ImagePlan p = view(img);
+    ImagePlan p = geometry_view(img);
     p.flip = !p.flip;
     return make(p);
   }
@@ -1044,6 +1082,132 @@ std::shared_ptr<Array> ImageTone::apply_image(const std::shared_ptr<Array>& img)
   p.toned = true;
   p.tone_op = op_, p.tone_arg = arg_, p.tone_factor = factor_;
   return make(p);
+}
+
+// ---- affine warps: mark the plan -------------------------------------------------
+int32_t parse_resample(const std::string& op, const std::string& name) {
+  if (name == "nearest") return MXD_WARP_NEAREST;
+  if (name == "bilinear") return MXD_WARP_BILINEAR;
+  throw std::invalid_argument(op + ": unknown resample '" + name + "' (one of nearest, bilinear)");
+}
+
+const char* resample_name(int32_t mode) { return mode == MXD_WARP_BILINEAR ? "bilinear" : "nearest"; }
+
+std::array<double, 6> affine_rotate_matrix(int64_t w, int64_t h, double angle) {
+  // Image.rotate, operation for operation (volatile: every product and sum
+  // rounded to double, none contracted)
+  double a = std::fmod(angle, 360.0);
+  if (a < 0.0) a += 360.0;  // Python's angle % 360.0
+  const double r = -(a * (M_PI / 180.0));
+  auto round15 = [](double v) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.15f", v);
+    return std::strtod(buf, nullptr);
+  };
+  const double c = round15(std::cos(r)), s = round15(std::sin(r));
+  const double cx = (double)w / 2.0, cy = (double)h / 2.0;
+  volatile double x0 = c * (-cx), x1 = s * (-cy);
+  volatile double x2 = x0 + x1;
+  volatile double x3 = x2 + 0.0;
+  volatile double x4 = x3 + cx;
+  volatile double y0 = (-s) * (-cx), y1 = c * (-cy);
+  volatile double y2 = y0 + y1;
+  volatile double y3 = y2 + 0.0;
+  volatile double y4 = y3 + cy;
+  return {{c, s, x4, -s, c, y4}};
+}
+
+namespace {
+std::array<uint8_t, 4> warp_fill(const std::string& op, const std::array<int64_t, 3>& fill) {
+  std::array<uint8_t, 4> out{{0, 0, 0, 0}};
+  for (int k = 0; k < 3; k++) {
+    if (fill[k] < 0 || fill[k] > 255) throw std::invalid_argument(op + ": fill must be in 0..255");
+    out[k] = (uint8_t)fill[k];
+  }
+  return out;
+}
+}  // namespace
+
+std::string ImageAffine::name() const {
+  static const char* const fixed[] = {"image_affine", "image_shear", "image_translate", "image_affine_rotate"};
+  static const char* const random[] = {"image_affine", "image_random_shear", "image_random_translate",
+                                       "image_random_affine_rotate"};
+  return random_ ? random[kind_] : fixed[kind_];
+}
+
+ImageAffine::ImageAffine(std::string ikey, Kind kind, const std::vector<double>& v, int32_t mode,
+                         const std::array<int64_t, 3>& fill, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), kind_(kind), random_(false), v_(v), mode_(mode) {
+  if (v_.size() != (kind_ == kMatrix ? 6u : kind_ == kRotate ? 1u : 2u))
+    throw std::invalid_argument(name() + (kind_ == kMatrix ? ": matrix must have 6 entries" : ": bad arguments"));
+  for (double x : v_)
+    if (!std::isfinite(x)) throw std::invalid_argument(name() + ": arguments must be finite");
+  fill_ = warp_fill(name(), fill);
+}
+
+ImageAffine::ImageAffine(std::string ikey, Kind kind, const std::array<bool, 2>& has, const std::array<Range, 2>& range,
+                         int32_t mode, const std::array<int64_t, 3>& fill, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), kind_(kind), random_(true), has_(has), range_(range), mode_(mode) {
+  static const char* const names[2] = {"x", "y"};
+  for (int k = 0; k < 2; k++) {
+    if (!has_[k]) continue;
+    const std::string what = kind_ == kRotate ? "angle" : names[k];
+    if (!std::isfinite(range_[k].first) || !std::isfinite(range_[k].second))
+      throw std::invalid_argument(name() + ": " + what + " range must be finite");
+    if (range_[k].first > range_[k].second) throw std::invalid_argument(name() + ": " + what + " range has lo > hi");
+  }
+  fill_ = warp_fill(name(), fill);
+}
+
+std::vector<double> ImageAffine::params() const {
+  if (!random_) return v_;
+  std::vector<double> v(kind_ == kRotate ? 1 : 2, 0.0);
+  auto st = get_state();
+  for (size_t k = 0; k < v.size(); k++)
+    if (has_[k]) v[k] = std::uniform_real_distribution<double>(range_[k].first, range_[k].second)(st->gen);
+  return v;
+}
+
+std::shared_ptr<Array> ImageAffine::mark(const std::shared_ptr<Array>& img, const std::vector<double>& v) const {
+  if (img->shape(2) != 3)
+    throw std::runtime_error(name() + ": image must have 3 channels, not " + std::to_string(img->shape(2)));
+  ImagePlan p = view(img);
+  if (p.warped || p.toned || p.colored) {
+    // the launch runs one warp, before tone and colour: run what is pending, warp its bytes
+    img->data();
+    p = view(img);
+  }
+  mxd_warp w{};
+  w.mode = mode_;
+  std::memcpy(w.fill, fill_.data(), sizeof w.fill);
+  std::array<double, 6> m{{1, 0, 0, 0, 1, 0}};
+  if (kind_ == kMatrix) std::copy(v.begin(), v.end(), m.begin());
+  else if (kind_ == kShear) m[1] = v[0], m[3] = v[1];
+  else if (kind_ == kTranslate) m[2] = v[0], m[5] = v[1];
+  else m = affine_rotate_matrix(p.crop_w, p.crop_h, v[0]);
+  std::memcpy(w.m, m.data(), sizeof w.m);
+  if (mxd_warp_validate(&w, (int32_t)p.crop_w, (int32_t)p.crop_h) != MXD_OK) {
+    std::string msg = mxd_last_error();
+    const size_t at = msg.rfind(" (image 0)");
+    if (at != std::string::npos) msg.erase(at);
+    throw std::runtime_error(name() + ": " + msg);
+  }
+  p.warped = true;
+  p.warp_mode = mode_;
+  p.warp_fill = fill_;
+  p.warp_m = m;
+  return make(p);
+}
+
+std::shared_ptr<Array> ImageAffine::apply_image(const std::shared_ptr<Array>& img) const { return mark(img, params()); }
+
+// one draw, the same parameters (and, the frames being one size, matrix) for every frame
+std::shared_ptr<Array> ImageAffine::apply_video(const std::shared_ptr<Array>& video) const {
+  const std::vector<double> v = params();
+  std::vector<std::shared_ptr<Array>> frames;
+  for (int64_t i = 0; i < video->shape(0); i++) frames.push_back(mark(video_frame(video, i), v));
+  if (frames.empty()) throw std::runtime_error("applyVideo: empty video");
+  return stack_frames(frames);
 }
 
 namespace {

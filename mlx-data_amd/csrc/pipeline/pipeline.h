@@ -109,6 +109,16 @@ struct ImagePlan {
   bool toned = false;
   int32_t tone_op = 0, tone_arg = 0;
   float tone_factor = 0.0f;
+  // image_affine / _shear / _translate / _affine_rotate and their random
+  // forms: the launch warps the u8 RGB result of the geometry above (mxd_warp
+  // {warp_mode, warp_fill, warp_m}: Pillow's Image.transform(AFFINE)) before
+  // the tone op, the colour map and the output form, which compose after it.
+  // A warp op on a plan already warped, toned or coloured materialises it
+  // first, as any crop, flip, resize or image_rotate after a warp does.
+  bool warped = false;
+  int32_t warp_mode = 0;
+  std::array<uint8_t, 4> warp_fill{{0, 0, 0, 0}};
+  std::array<double, 6> warp_m{{1, 0, 0, 0, 1, 0}};
   int64_t channels() const;
 };
 
@@ -387,6 +397,49 @@ class ImageTone : public ImageOp {
 };
 // "posterize", ... of an mxd_tone_op (the op is image_<name>).
 const char* tone_name(int32_t op);
+
+// Per-image affine warps (an addition to the reference's surface): Pillow's
+// Image.transform(size, AFFINE, matrix, resample, fillcolor=fill) and
+// Image.rotate(angle, resample, fillcolor=fill) of the RGB result bytes, bit
+// for bit, fused into the batch launch.  The op only
+// marks the pending plan; the rotate matrix needs the image's size and is
+// made when the op is applied.  RGB images only: "image_shear: image must
+// have 3 channels, not N" otherwise.  Bad arguments throw
+// std::invalid_argument from the constructors; a matrix outside the bound of
+// the C calls throws their message when the op is applied.
+class ImageAffine : public ImageOp {
+ public:
+  enum Kind { kMatrix = 0, kShear = 1, kTranslate = 2, kRotate = 3 };
+  using Range = std::pair<double, double>;
+  // v: the six entries (kMatrix), x and y (kShear, kTranslate: pixels), the
+  // angle in degrees (kRotate).  mode: mxd_warp_mode.  fill: r, g, b in 0..255.
+  ImageAffine(std::string ikey, Kind kind, const std::vector<double>& v, int32_t mode,
+              const std::array<int64_t, 3>& fill, std::string okey);
+  // The random forms: one uniform double per given range from the thread's
+  // generator, x then y (kRotate: has[0] and range[0], the angle); a range
+  // that is not given draws nothing and leaves 0.  A video draws once.
+  ImageAffine(std::string ikey, Kind kind, const std::array<bool, 2>& has, const std::array<Range, 2>& range,
+              int32_t mode, const std::array<int64_t, 3>& fill, std::string okey);
+  std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+  std::shared_ptr<Array> apply_video(const std::shared_ptr<Array>& video) const override;
+
+ private:
+  std::string name() const;
+  std::vector<double> params() const;  // the fixed ones, or a draw
+  std::shared_ptr<Array> mark(const std::shared_ptr<Array>& img, const std::vector<double>& v) const;
+  Kind kind_;
+  bool random_;
+  std::vector<double> v_;
+  std::array<bool, 2> has_{{false, false}};
+  std::array<Range, 2> range_{};
+  int32_t mode_;
+  std::array<uint8_t, 4> fill_{{0, 0, 0, 0}};
+};
+// "nearest" / "bilinear" -> mxd_warp_mode (std::invalid_argument otherwise) and back.
+int32_t parse_resample(const std::string& op, const std::string& name);
+const char* resample_name(int32_t mode);
+// Pillow's Image.rotate matrix for expand=False about (w / 2, h / 2).
+std::array<double, 6> affine_rotate_matrix(int64_t w, int64_t h, double angle);
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the
 // centre (core::image::rotate -> affine), one GPU pixel-map launch.

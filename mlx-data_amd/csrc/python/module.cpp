@@ -331,6 +331,50 @@ void color_range(const py::object& v, const char* what, int k, std::array<bool, 
   }
 }
 
+// The affine ops' fill: a scalar or an (r, g, b) sequence of integers.
+std::array<int64_t, 3> warp_fill_arg(const std::string& op, const py::object& v) {
+  try {
+    if (py::isinstance<py::int_>(v)) {
+      const int64_t f = v.cast<int64_t>();
+      return {{f, f, f}};
+    }
+    const auto rgb = v.cast<std::vector<int64_t>>();
+    if (rgb.size() == 3) return {{rgb[0], rgb[1], rgb[2]}};
+  } catch (const py::cast_error&) {
+  }
+  throw std::invalid_argument(op + ": fill must be an integer or an (r, g, b) sequence of integers");
+}
+
+// The random affine ops' arguments: None or a (lo, hi) pair each.
+void warp_range(const std::string& op, const py::object& v, const char* what, int k, std::array<bool, 2>& has,
+                std::array<ImageAffine::Range, 2>& range) {
+  has[k] = !v.is_none();
+  if (!has[k]) return;
+  try {
+    range[k] = v.cast<std::pair<double, double>>();
+  } catch (const py::cast_error&) {
+    throw std::invalid_argument(op + ": " + what + " must be None or a (lo, hi) pair");
+  }
+}
+
+std::shared_ptr<ImageAffine> affine_op(const char* op, const std::string& key, ImageAffine::Kind kind,
+                                       const std::vector<double>& v, const std::string& resample, const py::object& fill,
+                                       const std::string& output_key) {
+  return std::make_shared<ImageAffine>(key, kind, v, parse_resample(op, resample), warp_fill_arg(op, fill), output_key);
+}
+
+std::shared_ptr<ImageAffine> random_affine_op(const char* op, const std::string& key, ImageAffine::Kind kind,
+                                              const py::object& a, const char* a_name, const py::object& b,
+                                              const std::string& resample, const py::object& fill,
+                                              const std::string& output_key) {
+  std::array<bool, 2> has{};
+  std::array<ImageAffine::Range, 2> range{};
+  warp_range(op, a, a_name, 0, has, range);
+  if (kind != ImageAffine::kRotate) warp_range(op, b, "y", 1, has, range);
+  return std::make_shared<ImageAffine>(key, kind, has, range, parse_resample(op, resample), warp_fill_arg(op, fill),
+                                       output_key);
+}
+
 // ------------------------------------------------------------ dataset ops
 // The ops every Dataset (Buffer and Stream) carries (wrap_dataset.h).
 template <class D, class Wrap>
@@ -485,7 +529,76 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
           [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
             return wrap(self, std::make_shared<ImageTone>(key, MXD_TONE_CONTRAST, 0, factor, output_key));
           },
-          py::arg("key"), py::arg("factor"), py::arg("output_key") = "");
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
+      .def(
+          "image_affine",
+          [wrap](const Self& self, const std::string& key, const py::object& matrix, const std::string& resample,
+                 const py::object& fill, const std::string& output_key) {
+            std::vector<double> m;
+            try {
+              m = matrix.cast<std::vector<double>>();
+            } catch (const py::cast_error&) {
+              throw std::invalid_argument("image_affine: matrix must be a sequence of 6 numbers");
+            }
+            if (m.size() != 6) throw std::invalid_argument("image_affine: matrix must be a sequence of 6 numbers");
+            return wrap(self, affine_op("image_affine", key, ImageAffine::kMatrix, m, resample, fill, output_key));
+          },
+          py::arg("key"), py::arg("matrix"), py::arg("resample") = "nearest", py::arg("fill") = 0,
+          py::arg("output_key") = "")
+      .def(
+          "image_shear",
+          [wrap](const Self& self, const std::string& key, double x, double y, const std::string& resample,
+                 const py::object& fill, const std::string& output_key) {
+            return wrap(self, affine_op("image_shear", key, ImageAffine::kShear, {x, y}, resample, fill, output_key));
+          },
+          py::arg("key"), py::arg("x") = 0.0, py::arg("y") = 0.0, py::arg("resample") = "nearest", py::arg("fill") = 0,
+          py::arg("output_key") = "")
+      .def(
+          "image_translate",
+          [wrap](const Self& self, const std::string& key, double x, double y, const std::string& resample,
+                 const py::object& fill, const std::string& output_key) {
+            return wrap(self,
+                        affine_op("image_translate", key, ImageAffine::kTranslate, {x, y}, resample, fill, output_key));
+          },
+          py::arg("key"), py::arg("x") = 0.0, py::arg("y") = 0.0, py::arg("resample") = "nearest", py::arg("fill") = 0,
+          py::arg("output_key") = "")
+      .def(
+          "image_affine_rotate",
+          [wrap](const Self& self, const std::string& key, double angle, const std::string& resample,
+                 const py::object& fill, const std::string& output_key) {
+            return wrap(self,
+                        affine_op("image_affine_rotate", key, ImageAffine::kRotate, {angle}, resample, fill, output_key));
+          },
+          py::arg("key"), py::arg("angle"), py::arg("resample") = "nearest", py::arg("fill") = 0,
+          py::arg("output_key") = "")
+      .def(
+          "image_random_shear",
+          [wrap](const Self& self, const std::string& key, const py::object& x, const py::object& y,
+                 const std::string& resample, const py::object& fill, const std::string& output_key) {
+            return wrap(self, random_affine_op("image_random_shear", key, ImageAffine::kShear, x, "x", y, resample, fill,
+                                               output_key));
+          },
+          py::arg("key"), py::arg("x") = py::none(), py::arg("y") = py::none(), py::arg("resample") = "nearest",
+          py::arg("fill") = 0, py::arg("output_key") = "")
+      .def(
+          "image_random_translate",
+          [wrap](const Self& self, const std::string& key, const py::object& x, const py::object& y,
+                 const std::string& resample, const py::object& fill, const std::string& output_key) {
+            return wrap(self, random_affine_op("image_random_translate", key, ImageAffine::kTranslate, x, "x", y, resample,
+                                               fill, output_key));
+          },
+          py::arg("key"), py::arg("x") = py::none(), py::arg("y") = py::none(), py::arg("resample") = "nearest",
+          py::arg("fill") = 0, py::arg("output_key") = "")
+      .def(
+          "image_random_affine_rotate",
+          [wrap](const Self& self, const std::string& key, const py::object& angle, const std::string& resample,
+                 const py::object& fill, const std::string& output_key) {
+            if (angle.is_none()) throw std::invalid_argument("image_random_affine_rotate: angle must be a (lo, hi) pair");
+            return wrap(self, random_affine_op("image_random_affine_rotate", key, ImageAffine::kRotate, angle, "angle",
+                                               py::none(), resample, fill, output_key));
+          },
+          py::arg("key"), py::arg("angle"), py::arg("resample") = "nearest", py::arg("fill") = 0,
+          py::arg("output_key") = "");
 }
 
 using PadMap = std::unordered_map<std::string, double>;
@@ -735,6 +848,13 @@ PYBIND11_MODULE(_pipeline, m) {
       d["tone"] = py::make_tuple(tone_name(p.tone_op), arg);
     } else {
       d["tone"] = py::none();
+    }
+    // the warp: (resample, (r, g, b), the six entries)
+    if (p.warped) {
+      d["warp"] = py::make_tuple(resample_name(p.warp_mode), py::make_tuple(p.warp_fill[0], p.warp_fill[1], p.warp_fill[2]),
+                                 py::make_tuple(p.warp_m[0], p.warp_m[1], p.warp_m[2], p.warp_m[3], p.warp_m[4], p.warp_m[5]));
+    } else {
+      d["warp"] = py::none();
     }
     return d;
   });

@@ -235,6 +235,31 @@ int launch_tone(const ToneRowDev* rows, int nimgs, int hist_blocks, int row_bloc
                 bool matrix, void* stream);
 // Whether op reads the image's statistics.
 inline bool tone_needs_stats(int op) { return op >= 3; }
+// The warp stage (warp.hip): between the resize launches and the second pass
+// of a warp call (mxd_warp), over u8 RGB scratch rows.  One entry per image; a
+// workgroup takes one kWarpTileW x kWarpTileH output tile of one image, tiles
+// numbered through tile_begin.  warp_tab (one workgroup per image of path
+// kWarpTable, launched only when there is one) first writes the index tables
+// xt[w], yt[h] (int32) at tab_off in the workspace.
+constexpr int kWarpTileW = 64, kWarpTileH = 16;
+// An image's code path: its bytes copied, 16.16 fixed point, double bilinear, table lookup.
+enum WarpPath : int32_t { kWarpCopy = 0, kWarpFixed = 1, kWarpBilinear = 2, kWarpTable = 3 };
+struct WarpRowDev {
+  const uint8_t* src;  // u8 rows (16-byte aligned base, stride a multiple of 16)
+  uint8_t* dst;        // scratch rows like src, or the caller's u8 destination (any alignment)
+  int64_t src_stride, dst_stride;
+  int32_t w, h;
+  int32_t tile_begin;  // first of the image's workgroups among the launch's
+  int32_t tiles_x;     // tiles per tile row
+  int32_t path;        // WarpPath
+  uint32_t fill;       // r | g << 8 | b << 16
+  int32_t tab_off;     // kWarpTable: the image's tables in the workspace (bytes)
+  int32_t tab_index;   // kWarpTable: its warp_tab workgroup; -1 otherwise
+  double m[6];         // mxd_warp::m
+};
+static_assert(sizeof(WarpRowDev) == 112, "WarpRowDev layout");
+// tab_rows: how many entries take the table path; ws: the tables' workspace.
+int launch_warp(const WarpRowDev* rows, int nimgs, int ntiles, int tab_rows, uint8_t* ws, void* stream);
 // Waves of this configuration the device runs at once (occupancy x CUs), 0 if unknown.
 int wave_capacity(const WaveCfg& cfg, int device);
 // Diagnostics: the occupancy API's blocks per CU, the kernel's VGPRs and LDS

@@ -46,6 +46,8 @@ EXPORTS = (
     "mxd_resize_crop_to_device_color", "mxd_jpeg_resize_crop_to_device_color",
     "mxd_tone_table_u8", "mxd_tone_apply_u8", "mxd_resize_crop_batch_tone",
     "mxd_resize_crop_to_device_tone", "mxd_jpeg_resize_crop_to_device_tone",
+    "mxd_warp_validate", "mxd_warp_apply_u8", "mxd_resize_crop_batch_warp", "mxd_resize_crop_to_device_warp",
+    "mxd_jpeg_resize_crop_to_device_warp",
 )
 
 MXD_ELEM_F32 = 0
@@ -402,6 +404,63 @@ def resize_crop_to_device_tone(images, tones, colors, n, out_dtype=MXD_U8, fmt=N
 
 def jpeg_resize_crop_to_device_tone(images, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
     check(lib().mxd_jpeg_resize_crop_to_device_tone(images, tones, colors, n, out_dtype, _fmt_ref(fmt), device))
+
+
+MXD_WARP_NONE = 0
+MXD_WARP_NEAREST = 1
+MXD_WARP_BILINEAR = 2
+
+
+class MxdWarp(ctypes.Structure):
+    """struct mxd_warp (include/mxd_amd.h): a resampling mode, a fill colour, Pillow's AFFINE data."""
+
+    _fields_ = [("mode", ctypes.c_int32), ("fill", ctypes.c_uint8 * 4), ("m", ctypes.c_double * 6)]
+
+
+def make_warps(warps):
+    """(mode, fill, matrix) tuples (or MxdWarp values) -> ctypes array of mxd_warp.
+    fill: a scalar or (r, g, b); matrix: six numbers (None with MXD_WARP_NONE)."""
+    arr = (MxdWarp * max(1, len(warps)))()
+    for i, w in enumerate(warps):
+        if isinstance(w, MxdWarp):
+            arr[i] = w
+            continue
+        mode, fill, matrix = w
+        arr[i].mode = int(mode)
+        rgb = (fill,) * 3 if np.isscalar(fill) else tuple(fill)
+        for k in range(3):
+            arr[i].fill[k] = int(rgb[k])
+        for k in range(6):
+            arr[i].m[k] = float(matrix[k]) if matrix is not None else 0.0
+    return arr
+
+
+def warp_apply_u8(rgb, warp, out=None):
+    """mxd_warp_apply_u8: the CPU statement of a warp on an (h, w, 3) uint8 image
+    (any row stride); out: an (h, w, 3) uint8 array to write (default: a new one)."""
+    assert rgb.dtype == np.uint8 and rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.strides[1:] == (3, 1)
+    h, w = rgb.shape[:2]
+    if out is None:
+        out = np.empty((h, w, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.shape == rgb.shape and out.strides[1:] == (3, 1)
+    check(lib().mxd_warp_apply_u8(ctypes.c_void_p(rgb.ctypes.data), w, h, ctypes.c_int64(rgb.strides[0]),
+                                  make_warps([warp]), ctypes.c_void_p(out.ctypes.data),
+                                  ctypes.c_int64(out.strides[0])))
+    return out
+
+
+def resize_crop_batch_warp(images, warps, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0, stream=None):
+    check(lib().mxd_resize_crop_batch_warp(images, warps, tones, colors, n, out_dtype, _fmt_ref(fmt), device,
+                                           ctypes.c_void_p(stream)))
+
+
+def resize_crop_to_device_warp(images, warps, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_resize_crop_to_device_warp(images, warps, tones, colors, n, out_dtype, _fmt_ref(fmt), device))
+
+
+def jpeg_resize_crop_to_device_warp(images, warps, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_jpeg_resize_crop_to_device_warp(images, warps, tones, colors, n, out_dtype, _fmt_ref(fmt),
+                                                    device))
 
 
 def set_kernel_policy(policy):

@@ -97,6 +97,28 @@ second tone op, or a tone op after a colour op materialises what is pending.
 A video's frames each use their own statistics.  Bad arguments raise
 ``ValueError`` when the op is made.
 
+The affine warps of the augmentation policies stay in the launch too (the
+fifth addition): ``image_affine(key, matrix)`` (six numbers, Pillow's AFFINE
+data: output pixel -> source position), ``image_shear(key, x=0.0, y=0.0)``,
+``image_translate(key, x=0.0, y=0.0)`` (pixels; the content moves by -t, as in
+timm) and ``image_affine_rotate(key, angle)`` (degrees, Pillow's sign, about
+the centre, same size), each with ``resample="nearest" | "bilinear"``,
+``fill=0`` (a scalar or ``(r, g, b)`` in 0..255) and ``output_key=""``, and
+the random forms ``image_random_shear(key, x=None, y=None)``,
+``image_random_translate(key, x=None, y=None)`` and
+``image_random_affine_rotate(key, angle)`` with ``(lo, hi)`` pairs (one
+uniform draw per given range, x then y; a video draws once), all with ``_if``
+forms.  They are Pillow's ``Image.transform(size, AFFINE, ..., fillcolor=)``
+and ``Image.rotate(angle, resample, fillcolor=)`` on the uint8 result, bit for
+bit; ``image_rotate`` stays the reference's op.  RGB images only.  The op only
+marks the pending image and ``batch`` warps behind the resize of the same
+call.  The stage order in a launch is geometry, warp, tone, colour, output
+form: crops and flips before the warp are part of what it marks, tone and
+colour ops, ``image_to_float`` and ``image_normalize`` compose after it, and a
+crop, flip, resize or ``image_rotate`` after a warp, or a warp after a warp,
+tone or colour op, materialises what is pending.  Bad arguments raise
+``ValueError`` when the op is made.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole
@@ -157,7 +179,9 @@ def _add_if_variants(cls):
                  "image_center_crop", "image_random_crop", "image_random_h_flip", "image_random_area_crop",
                  "image_rotate", "image_channel_reduction", "image_to_float", "image_normalize",
                  "image_color_twist", "image_color_matrix", "image_random_color_twist",
-                 "image_posterize", "image_solarize", "image_autocontrast", "image_equalize", "image_contrast"):
+                 "image_posterize", "image_solarize", "image_autocontrast", "image_equalize", "image_contrast",
+                 "image_affine", "image_shear", "image_translate", "image_affine_rotate", "image_random_shear",
+                 "image_random_translate", "image_random_affine_rotate"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 
