@@ -67,12 +67,17 @@ extern "C" {
  * per-image affine warps -- mxd_warp_mode, mxd_warp, mxd_warp_validate,
  * mxd_warp_apply_u8,
  * mxd_resize_crop_batch_warp, mxd_resize_crop_to_device_warp,
- * mxd_jpeg_resize_crop_to_device_warp. */
+ * mxd_jpeg_resize_crop_to_device_warp.
+ * 7, added without a new number (test for MXD_HAS_ENHANCE / the symbols): the
+ * per-image enhance operations -- mxd_enhance_op, mxd_enhance,
+ * mxd_enhance_validate, mxd_enhance_apply_u8, mxd_resize_crop_batch_enhance,
+ * mxd_resize_crop_to_device_enhance, mxd_jpeg_resize_crop_to_device_enhance. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
 #define MXD_HAS_TONE 1
 #define MXD_HAS_WARP 1
+#define MXD_HAS_ENHANCE 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -708,6 +713,81 @@ int mxd_resize_crop_to_device_warp(const mxd_image* images, const mxd_warp* warp
 int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_warp* warps, const mxd_tone* tones,
                                         const mxd_color* colors, int32_t n, int32_t out_dtype,
                                         const mxd_out_format* fmt, int32_t device);
+
+/* ---- per-image enhance operations (ABI 7 additions; feature test: MXD_HAS_ENHANCE)
+ *
+ * An enhance operation acts on the u8 RGB result of an image's geometry and
+ * warp -- the crop_w x crop_h window, exactly what MXD_U8 gives after
+ * mxd_warp -- and produces a u8 RGB image of the same size: Pillow's
+ * ImageEnhance.Sharpness / Color / Brightness, that is
+ * Image.blend(degenerate, image, factor), bit for bit.  (The fourth member of
+ * the family, ImageEnhance.Contrast, is MXD_TONE_CONTRAST.)  For a pixel with
+ * bytes q0, q1, q2 the degenerate byte D_c of channel c is
+ *
+ *   BRIGHTNESS  D_c = 0
+ *   COLOR       D_c = L = (19595 q0 + 38470 q1 + 7471 q2 + 32768) >> 16, in
+ *               integers: the luma of the tone operations
+ *   SHARPNESS   Pillow's ImageFilter.SMOOTH: the outermost ring of the window
+ *               is copied, D_c = q_c, and so is every pixel when w < 3 or
+ *               h < 3; an interior pixel takes S = the sum of its 3 x 3
+ *               neighbourhood in channel c plus 4 x the centre, and
+ *               D_c = (2 S + 13) / 26 in integer division (equal to Pillow's
+ *               float32 trunc(sum k p + 0.5), k = 1/13, 5/13, for every
+ *               input: the exact value is never closer than 1/26 to an
+ *               integer).  The neighbourhood is the window's own: after the
+ *               mirror, after the warp, fill pixels included; nothing outside
+ *               the window is read.
+ *
+ * and the result, for the factor f, in float32 with each operation rounded and
+ * none fused, is x = (float)D_c + f * (float)(q_c - D_c); q'_c = (uint8)
+ * trunc(x) for 0 <= f <= 1, else 0 for x <= 0, 255 for x >= 255, trunc(x)
+ * between: MXD_TONE_CONTRAST's rule.  Factor 1 returns q, factor 0 returns D.
+ *
+ * In a call the stage order is geometry, warp, enhance, tone, colour, output
+ * form: the tone statistics are those of the enhanced bytes. */
+enum mxd_enhance_op {
+  MXD_ENHANCE_NONE = 0,
+  MXD_ENHANCE_SHARPNESS = 1,
+  MXD_ENHANCE_COLOR = 2,
+  MXD_ENHANCE_BRIGHTNESS = 3
+};
+
+typedef struct mxd_enhance {
+  int32_t op;          /* mxd_enhance_op; NONE: the image's bytes stay as they are, factor is not read */
+  float factor;        /* f: finite, 0 <= f <= 1e6 */
+  int32_t reserved[2]; /* must be 0 */
+} mxd_enhance;
+
+/* Host only: the CPU statement of the arithmetic above on the w x h packed
+ * RGB pixels at rgb (rows stride bytes apart) into out (rows out_stride bytes
+ * apart).  out must not overlap rgb: SHARPNESS reads the neighbours of a pixel
+ * after that pixel is written.  MXD_ERR_INVALID for a bad enh (as the calls
+ * below). */
+int mxd_enhance_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, int64_t stride, const mxd_enhance* enh,
+                         uint8_t* out, int64_t out_stride);
+/* Host only: the checks the calls below make of one entry (MXD_OK, or
+ * MXD_ERR_INVALID with their message). */
+int mxd_enhance_validate(const mxd_enhance* enh);
+
+/* The _warp calls with enhances[i] applied to images[i]'s result after
+ * warps[i] and before tones[i].  warps, tones, colors and fmt may each be
+ * NULL; enhances may not.  Device destinations only.  MXD_ERR_INVALID (the
+ * message names the image and the field) for a null enhances, an unknown op,
+ * a negative, non-finite or too large factor, a non-zero reserved, or
+ * channels != 3; everything is validated before any launch.  Every image is
+ * resized as a u8 image into a scratch by the kernels of the plain calls; one
+ * more launch on the same stream (enhance_rows) reads those rows, or the warp
+ * stage's, and writes the destinations when nothing follows, else the other
+ * of the two scratches, which the row stage of the _tone calls reads. */
+int mxd_resize_crop_batch_enhance(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                  const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                  const mxd_out_format* fmt, int32_t device, void* stream);
+int mxd_resize_crop_to_device_enhance(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                      const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                      const mxd_out_format* fmt, int32_t device);
+int mxd_jpeg_resize_crop_to_device_enhance(const mxd_jpeg_image* images, const mxd_warp* warps,
+                                           const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
+                                           int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
 
 /* Diagnostics: where a host-side pipeline's time goes, summed over every
  * thread since the last reset (reset != 0 zeroes them after reading).

@@ -437,6 +437,13 @@ int launch_warp_stage(const BatchLayout& L, const ImgDev* dev, void* stream) {
   return MXD_OK;
 }
 
+// The enhance stage of an enhance call: behind the warp stage, before the second pass.
+int launch_enhance_stage(const BatchLayout& L, const ImgDev* dev, void* stream) {
+  if (mxd::launch_enhance(reinterpret_cast<const mxd::EnhanceRowDev*>(dev + L.enhance_at), L.n, L.enhance_tiles, stream))
+    return fail(MXD_ERR_DEVICE, std::string("enhance launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return MXD_OK;
+}
+
 // One launchable batch: its layout, the upload, the launches.
 int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
                    const Stored* stored, const PostOps& ops) {
@@ -456,6 +463,7 @@ int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_
   // The second pass, behind the joins: every resize kernel that wrote scratch
   // rows is ordered before it on the caller's stream.
   if (launch_rc == MXD_OK && L.warped) launch_rc = launch_warp_stage(L, dev, stream);
+  if (launch_rc == MXD_OK && L.enhanced) launch_rc = launch_enhance_stage(L, dev, stream);
   if (launch_rc == MXD_OK) launch_rc = launch_second_pass(L, dev, ofd, stream);
   // The batch is counted on a failed launch too (see launch_all).
   const int rel = release_descs(ws, stream, hit);
@@ -469,6 +477,8 @@ int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* 
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
   if (ops->warps)
     if (int rc = warp_validate(images, ops->warps, n)) return rc;
+  if (ops->enhances)
+    if (int rc = enhance_validate(images, ops->enhances, n)) return rc;
   if (ops->tones)
     if (int rc = tone_validate(images, ops->tones, n)) return rc;
   if (ops->colors)

@@ -347,14 +347,16 @@ mxd::FmtRowDev entry_head(const mxd_image& im, const mxd_image& caller, int32_t 
 // Whether a warp takes the table path: Pillow's scale path of NEAREST.
 bool warp_tabled(const mxd_warp& w) { return w.mode == MXD_WARP_NEAREST && w.m[1] == 0.0 && w.m[3] == 0.0; }
 
-// A warp call's scratch behind the rows A the resize kernels write: rows B
-// when a second pass follows the warp stage, then the index tables.
+// A warp or enhance call's scratch behind the rows A the resize kernels
+// write: rows B when a second pass or the enhance stage follows the first
+// stage, then a warp call's index tables.
 void place_warp_scratch(Batch& b, const PostOps& ops) {
   BatchLayout& L = b.L;
-  if (L.pass != SecondPass::None) {
+  if (L.pass != SecondPass::None || (L.warped && L.enhanced)) {
     L.warp_b_at = (L.scratch_bytes + 255) & ~(size_t)255;
     L.scratch_bytes = L.warp_b_at + L.scratch_bytes;
   }
+  if (!L.warped) return;
   L.warp_tab_at = (L.scratch_bytes + 255) & ~(size_t)255;
   size_t tab_bytes = 0;
   for (int32_t i = 0; i < b.n; i++)
@@ -380,7 +382,7 @@ void append_warps(Batch& b, const mxd_image* callers, const PostOps& ops) {
     mxd::WarpRowDev& e = L.warp_entry(i);
     e.src = static_cast<const uint8_t*>(im.dst);
     e.src_stride = im.dst_stride;
-    if (L.pass != SecondPass::None) {
+    if (L.pass != SecondPass::None || L.enhanced) {
       e.dst = static_cast<uint8_t*>(im.dst) + L.warp_b_at;
       e.dst_stride = im.dst_stride;
     } else {
@@ -407,6 +409,37 @@ void append_warps(Batch& b, const mxd_image* callers, const PostOps& ops) {
   }
 }
 
+// The enhance stage's entries, in batch order, behind the warp stage's: ops
+// and factors are part of its bytes, so a cached slot is reused only for the
+// same ones.  It reads what the stage before it wrote (rows A, or the warp's
+// rows B) and writes the other rows, or the destinations when nothing follows.
+void append_enhances(Batch& b, const mxd_image* callers, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  L.enhance_at = L.descs.size();
+  L.descs.resize(L.enhance_at + ((size_t)b.n * sizeof(mxd::EnhanceRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
+  for (int32_t i = 0; i < b.n; i++) {
+    const mxd_image& im = L.images[i];
+    const mxd_enhance& en = ops.enhances[i];
+    mxd::EnhanceRowDev& e = L.enhance_entry(i);
+    e.src = static_cast<const uint8_t*>(im.dst) + (L.warped ? L.warp_b_at : 0);
+    e.src_stride = im.dst_stride;
+    if (L.pass != SecondPass::None) {
+      e.dst = static_cast<uint8_t*>(im.dst) + (L.warped ? 0 : L.warp_b_at);
+      e.dst_stride = im.dst_stride;
+    } else {
+      e.dst = static_cast<uint8_t*>(callers[i].dst);
+      e.dst_stride = callers[i].dst_stride;
+    }
+    e.w = im.crop_w, e.h = im.crop_h;
+    e.tile_begin = L.enhance_tiles;
+    e.tiles_x = (im.crop_w + mxd::kEnhTileW - 1) / mxd::kEnhTileW;
+    L.enhance_tiles += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
+    e.op = en.op;
+    // (MXD_ENHANCE_NONE reads no factor: zero, so equal calls make equal bytes)
+    e.factor = en.op == MXD_ENHANCE_NONE ? 0.0f : en.factor;
+  }
+}
+
 // After every descriptor, in ImgDev-sized blocks: the unit -> image tables of
 // the band launches whose images differ in unit count (int32 each), then the
 // second pass's entries: part of the upload's bytes, so a cached slot is
@@ -429,7 +462,7 @@ void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
   if (!unit_tables.empty())
     std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.tables_at), unit_tables.data(), unit_tables.size() * 4);
   L.fmt_at = L.descs.size();
-  if (L.warped) place_warp_scratch(b, ops);
+  if (L.warped || L.enhanced) place_warp_scratch(b, ops);
   if (L.pass == SecondPass::None) return;
   for (int32_t i = 0; i < b.n; i++) L.fmt_count += second_pass_reads(b, i) ? 1 : 0;
   L.descs.resize(L.fmt_at + ((size_t)L.fmt_count * L.entry_size + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
@@ -440,7 +473,8 @@ void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
     const mxd_image& im = L.images[i];
     mxd::FmtRowDev& head = L.entry(j++);
     head = entry_head(im, callers[i], L.fmt_blocks);
-    head.src += L.warp_b_at;  // (a warp call: the warp stage's rows)
+    // (a warp or an enhance call: the stage's rows B; both: the enhance stage's, A again)
+    if (!(L.warped && L.enhanced)) head.src += L.warp_b_at;
     L.fmt_blocks += (im.crop_h + block_rows - 1) / block_rows;
     if (L.pass == SecondPass::Format) continue;
     mxd::ColorRowDev& c = reinterpret_cast<mxd::ColorRowDev&>(head);
@@ -481,10 +515,16 @@ void BatchLayout::add_scratch(uint8_t* base) {
     for (int32_t i = 0; i < n; i++) {
       mxd::WarpRowDev& e = warp_entry(i);
       e.src = base + reinterpret_cast<uintptr_t>(e.src);
-      if (pass != SecondPass::None) e.dst = base + reinterpret_cast<uintptr_t>(e.dst);
+      if (pass != SecondPass::None || enhanced) e.dst = base + reinterpret_cast<uintptr_t>(e.dst);
     }
     warp_tab = base + warp_tab_at;
   }
+  if (enhanced)
+    for (int32_t i = 0; i < n; i++) {
+      mxd::EnhanceRowDev& e = enhance_entry(i);
+      e.src = base + reinterpret_cast<uintptr_t>(e.src);
+      if (pass != SecondPass::None) e.dst = base + reinterpret_cast<uintptr_t>(e.dst);
+    }
 }
 
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
@@ -499,6 +539,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
                                                 : 0;
   L.matrix = ops.colors != nullptr;
   L.warped = ops.warps != nullptr;
+  L.enhanced = ops.enhances != nullptr;
   // A formatted call plans its kernels as a u8 call does: the wave kernels
   // exist in the same shapes in every output mode and write any element
   // alignment, and an image they do not take is resized into u8 scratch rows
@@ -528,6 +569,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = general_group(b)) return rc;
   append_tables(b, callers, ops);
   if (L.warped) append_warps(b, callers, ops);
+  if (L.enhanced) append_enhances(b, callers, ops);
   // Largest first (a band unit is a workgroup, ~4 wave units).
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});

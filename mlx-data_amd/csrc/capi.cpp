@@ -184,6 +184,16 @@ static int warp_ops(const mxd_out_format* fmt, const mxd_color* colors, const mx
   return MXD_OK;
 }
 
+// The head of the _enhance entry points: enhances required, everything else optional.
+static int enhance_ops(const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones, const mxd_warp* warps,
+                       const mxd_enhance* enhances, int32_t n, PostOps* ops) {
+  if (fmt)
+    if (int rc = fmt_validate(fmt, 0)) return rc;
+  if (n > 0 && !enhances) return fail(MXD_ERR_INVALID, "mxd: null enhances");
+  *ops = n > 0 ? PostOps{fmt, colors, tones, warps, enhances} : PostOps{fmt};
+  return MXD_OK;
+}
+
 extern "C" {
 
 int mxd_abi_version(void) { return MXD_ABI_VERSION; }
@@ -293,6 +303,14 @@ int mxd_resize_crop_batch_warp(const mxd_image* images, const mxd_warp* warps, c
                                int32_t device, void* stream) {
   PostOps ops;
   if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
+  return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
+}
+
+int mxd_resize_crop_batch_enhance(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                  const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                  const mxd_out_format* fmt, int32_t device, void* stream) {
+  PostOps ops;
+  if (int rc = enhance_ops(fmt, colors, tones, warps, enhances, n, &ops)) return rc;
   return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
@@ -508,6 +526,14 @@ int mxd_resize_crop_to_device_warp(const mxd_image* images, const mxd_warp* warp
   return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
+int mxd_resize_crop_to_device_enhance(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                      const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t out_dtype,
+                                      const mxd_out_format* fmt, int32_t device) {
+  PostOps ops;
+  if (int rc = enhance_ops(fmt, colors, tones, warps, enhances, n, &ops)) return rc;
+  return host_path(images, n, out_dtype, device, true, nullptr, ops);
+}
+
 int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device) {
   if (int rc = fmt_validate(fmt, 0)) return rc;
   return host_path(images, n, MXD_U8, device, true, nullptr, PostOps{fmt});
@@ -623,6 +649,14 @@ int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_
                                         const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
   if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
+  return jpeg_path(images, n, out_dtype, device, true, ops);
+}
+
+int mxd_jpeg_resize_crop_to_device_enhance(const mxd_jpeg_image* images, const mxd_warp* warps,
+                                           const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
+                                           int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
+  PostOps ops;
+  if (int rc = enhance_ops(fmt, colors, tones, warps, enhances, n, &ops)) return rc;
   return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 

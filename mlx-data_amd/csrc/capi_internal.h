@@ -267,6 +267,8 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
 // call, colors[i] belongs to images[i].  tones: a tone call, tones[i] belongs
 // to images[i]; colors may be null then (no matrix).  warps: a warp call,
 // warps[i] belongs to images[i]; every other member may be null then.
+// enhances: an enhance call, enhances[i] belongs to images[i]; every other
+// member may be null then.
 // The second pass (row_stage.hip) such a call launches behind its resize
 // kernels: format_rows for the images of a formatted call that no wave kernel
 // takes, pixel_rows for every image of a colour or tone call.  A warp call
@@ -274,22 +276,29 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
 // (warp.hip) in front of the second pass, which then reads every image (a
 // format alone: through pixel_rows with identity matrices) from the warp's
 // scratch rows B; with no second pass the warp stage writes the u8
-// destinations itself.
+// destinations itself.  An enhance call runs the enhance stage (enhance.hip)
+// behind the warp stage, if any: it reads A and writes B without a warp, reads
+// B and writes A (dead by then) with one, or the u8 destinations when no
+// second pass follows; the second pass reads the rows the last stage wrote.
 enum class SecondPass : int32_t { None, Format, Color, Tone };
 struct PostOps {
   const mxd_out_format* fmt = nullptr;
   const mxd_color* colors = nullptr;
   const mxd_tone* tones = nullptr;
   const mxd_warp* warps = nullptr;
+  const mxd_enhance* enhances = nullptr;
   // (a format alone, or nullptr, converts: a formatted / plain call)
   PostOps(const mxd_out_format* f = nullptr, const mxd_color* c = nullptr, const mxd_tone* t = nullptr,
-          const mxd_warp* w = nullptr)
-      : fmt(f), colors(c), tones(t), warps(w) {}
-  bool any() const { return fmt || colors || tones || warps; }
-  bool per_image() const { return colors || tones || warps; }  // a colour, tone or warp call
+          const mxd_warp* w = nullptr, const mxd_enhance* e = nullptr)
+      : fmt(f), colors(c), tones(t), warps(w), enhances(e) {}
+  bool any() const { return fmt || colors || tones || warps || enhances; }
+  bool per_image() const { return colors || tones || warps || enhances; }  // a colour, tone, warp or enhance call
   SecondPass pass() const {
-    // (a warp call with a format alone: pixel_rows with the identity, which is exact)
-    return tones ? SecondPass::Tone : colors || (warps && fmt) ? SecondPass::Color : fmt ? SecondPass::Format : SecondPass::None;
+    // (a warp or enhance call with a format alone: pixel_rows with the identity, which is exact)
+    return tones                                  ? SecondPass::Tone
+           : colors || ((warps || enhances) && fmt) ? SecondPass::Color
+           : fmt                                  ? SecondPass::Format
+                                                  : SecondPass::None;
   }
   // The resize kernels write the format themselves (wave kernels in their
   // formatted mode).  A colour or tone call's run in their u8 mode into
@@ -298,7 +307,7 @@ struct PostOps {
   // The call's share for the images from `first` on (a host-path chunk).
   PostOps at(int32_t first) const {
     return PostOps{fmt, colors ? colors + first : nullptr, tones ? tones + first : nullptr,
-                   warps ? warps + first : nullptr};
+                   warps ? warps + first : nullptr, enhances ? enhances + first : nullptr};
   }
 };
 
@@ -367,6 +376,18 @@ struct BatchLayout {
   int32_t warp_tiles = 0, warp_tab_count = 0;
   uint8_t* warp_tab = nullptr;
   mxd::WarpRowDev& warp_entry(int32_t i) { return reinterpret_cast<mxd::WarpRowDev*>(descs.data() + warp_at)[i]; }
+  // Enhance call only.  After the warp stage's entries, from enhance_at, one
+  // EnhanceRowDev per image in batch order (enhance_tiles workgroups).
+  // Without a warp their src are rows A and their dst rows B (the second
+  // pass's src); with one their src are B, which the warp stage then always
+  // writes, and their dst rows A (the second pass's src).  With no second pass
+  // their dst are the caller's destinations.  No third scratch.
+  bool enhanced = false;
+  size_t enhance_at = 0;
+  int32_t enhance_tiles = 0;
+  mxd::EnhanceRowDev& enhance_entry(int32_t i) {
+    return reinterpret_cast<mxd::EnhanceRowDev*>(descs.data() + enhance_at)[i];
+  }
   const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
   void add_scratch(uint8_t* base);
 };
@@ -411,7 +432,7 @@ std::vector<SubBatch> split_batch(const mxd_image* images, int32_t n, const Stor
 int run_batch(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, void* stream,
               const Stored* stored = nullptr, PostOps ops = {});
 // The head of every colour and tone call (nothing to do for the others):
-// validates the warps, the tones, then the matrices, makes ops->fmt the format pixel_rows
+// validates the warps, the enhances, the tones, then the matrices, makes ops->fmt the format pixel_rows
 // writes (f32_fmt, the q / 255 table, for MXD_F32_DIV255; null stays null for
 // MXD_U8) and *out_dtype the form the kernels are planned in.
 int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* out_dtype, mxd_out_format* f32_fmt);
@@ -434,6 +455,11 @@ int tone_validate(const mxd_image* images, const mxd_tone* tones, int32_t n);
 int warp_validate(const mxd_image* images, const mxd_warp* warps, int32_t n);
 // One warp against a w x h image.
 int warp_validate_one(const mxd_warp& warp, int32_t w, int32_t h);
+
+// ---------------------------------------------------------------------------
+// Enhance operations (enhance.cpp).
+// enhances[i] against images[i] (images may be null: the entries alone).
+int enhance_validate(const mxd_image* images, const mxd_enhance* enhances, int32_t n);
 
 // ---------------------------------------------------------------------------
 // Formatted outputs (outfmt.cpp).

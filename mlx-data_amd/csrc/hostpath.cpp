@@ -677,6 +677,7 @@ int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
   // the second pass writes device destinations only
   if (!dst_device && ops.warps) return fail(MXD_ERR_UNSUPPORTED, "mxd: warp calls need device destinations");
+  if (!dst_device && ops.enhances) return fail(MXD_ERR_UNSUPPORTED, "mxd: enhance calls need device destinations");
   if (!dst_device && ops.tones) return fail(MXD_ERR_UNSUPPORTED, "mxd: tone calls need device destinations");
   if (!dst_device && ops.colors) return fail(MXD_ERR_UNSUPPORTED, "mxd: colour calls need device destinations");
   mxd_out_format f32_fmt;

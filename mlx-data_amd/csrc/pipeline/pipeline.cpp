@@ -264,7 +264,8 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
   std::vector<mxd_color> pc, jc;  // the colours of `plain` and `jp`, image for image
   std::vector<mxd_tone> pt, jt;   // and their tones
   std::vector<mxd_warp> pw, jw;   // and their warps
-  bool colored = false, toned = false, warped = false;
+  std::vector<mxd_enhance> pe, je;  // and their enhance ops
+  bool colored = false, toned = false, warped = false, enhanced = false;
   for (size_t i = 0; i < n; i++) {
     const Job& j = jobs[i];
     mxd_color c;
@@ -280,20 +281,42 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
       std::memcpy(w.m, j.plan.warp_m.data(), sizeof w.m);
     }
     warped = warped || j.plan.warped;
+    mxd_enhance e{};  // (MXD_ENHANCE_NONE for a plan without an enhance op)
+    if (j.plan.enhanced) e.op = j.plan.enhance_op, e.factor = j.plan.enhance_factor;
+    enhanced = enhanced || j.plan.enhanced;
     if (auto src = j.plan.src->jpeg()) {
       jp.push_back(jpeg_desc(j.plan, *src, j.dst, j.stride));
       jc.push_back(c);
       jt.push_back(t);
       jw.push_back(w);
+      je.push_back(e);
       keep.push_back(std::move(src));
     } else {
       plain.push_back(plan_desc(j.plan, j.dst, j.stride));
       pc.push_back(c);
       pt.push_back(t);
       pw.push_back(w);
+      pe.push_back(e);
     }
   }
   g_run_jpeg.fetch_add((int64_t)jp.size());
+  // Some plan is enhanced: the whole launch goes through the _enhance calls,
+  // plans without an enhance op with MXD_ENHANCE_NONE; warps, tones and
+  // matrices only if some plan has them.  Device destinations only.
+  if (enhanced) {
+    if (!dst_device) throw std::logic_error("mxd: an enhance launch needs device destinations");
+    mxd_out_format of{};
+    if (fmt) of = abi_format(*fmt, jobs[0]);
+    if (!jp.empty())
+      if (int rc = mxd_jpeg_resize_crop_to_device_enhance(jp.data(), warped ? jw.data() : nullptr, je.data(),
+                                                          toned ? jt.data() : nullptr, colored ? jc.data() : nullptr,
+                                                          (int32_t)jp.size(), dtype, fmt ? &of : nullptr, device))
+        return rc;
+    if (plain.empty()) return MXD_OK;
+    return mxd_resize_crop_to_device_enhance(plain.data(), warped ? pw.data() : nullptr, pe.data(),
+                                             toned ? pt.data() : nullptr, colored ? pc.data() : nullptr,
+                                             (int32_t)plain.size(), dtype, fmt ? &of : nullptr, device);
+  }
   // Some plan is warped: the whole launch goes through the _warp calls, plans
   // without a warp with MXD_WARP_NONE; tones and matrices only if some plan
   // has them.  Device destinations only.
@@ -518,8 +541,8 @@ void run_host(const std::vector<Job>& jobs, int32_t dtype, const OutFormat* fmt 
   const std::vector<Slice> sl = split_batch((int64_t)n, (int64_t)devs.size(), g_rr.fetch_add(k));
   // a coloured plan anywhere: every slice takes the device call and one copy
   // back, like a formatted batch (each slice carries its own jobs' matrices)
-  bool colored = false;  // (or toned, or warped: device calls only, too)
-  for (const Job& j : jobs) colored = colored || j.plan.colored || j.plan.toned || j.plan.warped;
+  bool colored = false;  // (or toned, warped or enhanced: device calls only, too)
+  for (const Job& j : jobs) colored = colored || j.plan.colored || j.plan.toned || j.plan.warped || j.plan.enhanced;
   auto slice = [&jobs, dtype, &devs, &sl, fmt, colored](size_t s) -> std::string {
     const Job* first = jobs.data() + sl[s].begin;
     const size_t count = (size_t)(sl[s].end - sl[s].begin);
@@ -730,7 +753,7 @@ std::shared_ptr<Array> plan_resize(const std::shared_ptr<Array>& img, int64_t dw
   // colour of transparent pixels, so it runs before the next one)
   const bool identity_so_far =
       p.resize_w == p.sw && p.resize_h == p.sh && !p.flip && !(p.resampled && p.channels() == 4) && !p.colored &&
-      !p.toned;
+      !p.toned && !p.enhanced;
   if (identity_so_far) {
     // crop-then-resize: the crop becomes the source window.
     p.sx += p.crop_x;
@@ -770,8 +793,8 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
     return out;
   }
   ImagePlan p = geometry_view(img);
-  if (p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) {
-    // the op's statistics are those of the window it saw: run it, crop its bytes
+  if ((p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) || (p.enhanced && p.enhance_op == MXD_ENHANCE_SHARPNESS)) {
+    // the op's statistics (SHARPNESS: copied ring) are those of the window it saw: run it, crop its bytes
     img->data();
     p = view(img);
   }
@@ -1172,8 +1195,8 @@ std::shared_ptr<Array> ImageAffine::mark(const std::shared_ptr<Array>& img, cons
   if (img->shape(2) != 3)
     throw std::runtime_error(name() + ": image must have 3 channels, not " + std::to_string(img->shape(2)));
   ImagePlan p = view(img);
-  if (p.warped || p.toned || p.colored) {
-    // the launch runs one warp, before tone and colour: run what is pending, warp its bytes
+  if (p.warped || p.enhanced || p.toned || p.colored) {
+    // the launch runs one warp, before enhance, tone and colour: run what is pending, warp its bytes
     img->data();
     p = view(img);
   }
@@ -1206,6 +1229,62 @@ std::shared_ptr<Array> ImageAffine::apply_video(const std::shared_ptr<Array>& vi
   const std::vector<double> v = params();
   std::vector<std::shared_ptr<Array>> frames;
   for (int64_t i = 0; i < video->shape(0); i++) frames.push_back(mark(video_frame(video, i), v));
+  if (frames.empty()) throw std::runtime_error("applyVideo: empty video");
+  return stack_frames(frames);
+}
+
+// ---- enhance ops: mark the plan ------------------------------------------------
+const char* enhance_name(int32_t op) {
+  static const char* const names[] = {"none", "sharpness", "color", "brightness"};
+  return op >= 0 && op <= MXD_ENHANCE_BRIGHTNESS ? names[op] : "none";
+}
+
+std::string ImageEnhance::name() const { return std::string(random_ ? "image_random_" : "image_") + enhance_name(op_); }
+
+namespace {
+bool enhance_factor_ok(double f) { return std::isfinite(f) && f >= 0.0 && f <= 1e6; }
+}  // namespace
+
+ImageEnhance::ImageEnhance(std::string ikey, int32_t op, double factor, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), op_(op), random_(false), lo_(factor), hi_(factor) {
+  if (!enhance_factor_ok(factor)) throw std::invalid_argument(name() + ": factor must be finite and in 0..1e6");
+}
+
+ImageEnhance::ImageEnhance(std::string ikey, int32_t op, std::pair<double, double> range, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), op_(op), random_(true), lo_(range.first), hi_(range.second) {
+  if (!enhance_factor_ok(lo_) || !enhance_factor_ok(hi_))
+    throw std::invalid_argument(name() + ": factor range must be finite and in 0..1e6");
+  if (lo_ > hi_) throw std::invalid_argument(name() + ": factor range has lo > hi");
+}
+
+double ImageEnhance::factor() const {
+  if (!random_) return lo_;
+  auto st = get_state();
+  return std::uniform_real_distribution<double>(lo_, hi_)(st->gen);
+}
+
+std::shared_ptr<Array> ImageEnhance::mark(const std::shared_ptr<Array>& img, double factor) const {
+  if (img->shape(2) != 3)
+    throw std::runtime_error(name() + ": image must have 3 channels, not " + std::to_string(img->shape(2)));
+  ImagePlan p = view(img);
+  if (p.enhanced || p.toned || p.colored) {
+    // the launch runs one enhance op, before tone and colour: run what is pending, enhance its bytes
+    img->data();
+    p = view(img);
+  }
+  p.enhanced = true;
+  p.enhance_op = op_;
+  p.enhance_factor = (float)factor;
+  return make(p);
+}
+
+std::shared_ptr<Array> ImageEnhance::apply_image(const std::shared_ptr<Array>& img) const { return mark(img, factor()); }
+
+// one draw, the same factor for every frame
+std::shared_ptr<Array> ImageEnhance::apply_video(const std::shared_ptr<Array>& video) const {
+  const double f = factor();
+  std::vector<std::shared_ptr<Array>> frames;
+  for (int64_t i = 0; i < video->shape(0); i++) frames.push_back(mark(video_frame(video, i), f));
   if (frames.empty()) throw std::runtime_error("applyVideo: empty video");
   return stack_frames(frames);
 }

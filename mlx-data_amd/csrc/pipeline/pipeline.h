@@ -119,6 +119,18 @@ struct ImagePlan {
   int32_t warp_mode = 0;
   std::array<uint8_t, 4> warp_fill{{0, 0, 0, 0}};
   std::array<double, 6> warp_m{{1, 0, 0, 0, 1, 0}};
+  // image_sharpness / _color / _brightness and their random forms: the launch
+  // applies mxd_enhance {enhance_op, enhance_factor} (Pillow's ImageEnhance)
+  // to the u8 RGB result of the geometry and the warp above, before the tone
+  // op, the colour map and the output form, which compose after it.  A flip
+  // composes after every enhance op and a crop after COLOR and BRIGHTNESS (they
+  // are pointwise, and SMOOTH is symmetric); a crop after SHARPNESS, whose
+  // copied ring is the uncropped window's, a resize, image_rotate, a warp op
+  // or a second enhance op materialises the plan first, as an enhance op on a
+  // plan already toned or coloured does.
+  bool enhanced = false;
+  int32_t enhance_op = 0;
+  float enhance_factor = 1.0f;
   int64_t channels() const;
 };
 
@@ -440,6 +452,33 @@ int32_t parse_resample(const std::string& op, const std::string& name);
 const char* resample_name(int32_t mode);
 // Pillow's Image.rotate matrix for expand=False about (w / 2, h / 2).
 std::array<double, 6> affine_rotate_matrix(int64_t w, int64_t h, double angle);
+
+// Per-image enhance operations (an addition to the reference's surface):
+// Pillow's ImageEnhance.Sharpness / Color / Brightness of the RGB result
+// bytes, bit for bit, fused into the batch launch.  The
+// op only marks the pending plan.  RGB images only: "image_sharpness: image
+// must have 3 channels, not N" otherwise.  Bad arguments throw
+// std::invalid_argument from the constructors.
+class ImageEnhance : public ImageOp {
+ public:
+  // op: mxd_enhance_op (not NONE); factor: finite, 0 <= factor <= 1e6.
+  ImageEnhance(std::string ikey, int32_t op, double factor, std::string okey);
+  // The random forms: one uniform double in [lo, hi] from the thread's
+  // generator per image; a video draws once for all its frames.
+  ImageEnhance(std::string ikey, int32_t op, std::pair<double, double> range, std::string okey);
+  std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+  std::shared_ptr<Array> apply_video(const std::shared_ptr<Array>& video) const override;
+
+ private:
+  std::string name() const;
+  double factor() const;  // the fixed one, or a draw
+  std::shared_ptr<Array> mark(const std::shared_ptr<Array>& img, double factor) const;
+  int32_t op_;
+  bool random_;
+  double lo_, hi_;
+};
+// "sharpness", "color", "brightness" of an mxd_enhance_op (the op is image_<name>).
+const char* enhance_name(int32_t op);
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the
 // centre (core::image::rotate -> affine), one GPU pixel-map launch.

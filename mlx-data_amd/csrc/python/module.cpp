@@ -375,6 +375,15 @@ std::shared_ptr<ImageAffine> random_affine_op(const char* op, const std::string&
                                        output_key);
 }
 
+// The random enhance ops' factor: a (lo, hi) pair.
+std::pair<double, double> enhance_range(const std::string& op, const py::object& v) {
+  try {
+    return v.cast<std::pair<double, double>>();
+  } catch (const py::cast_error&) {
+    throw std::invalid_argument(op + ": factor must be a (lo, hi) pair");
+  }
+}
+
 // ------------------------------------------------------------ dataset ops
 // The ops every Dataset (Buffer and Stream) carries (wrap_dataset.h).
 template <class D, class Wrap>
@@ -598,7 +607,46 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
                                                py::none(), resample, fill, output_key));
           },
           py::arg("key"), py::arg("angle"), py::arg("resample") = "nearest", py::arg("fill") = 0,
-          py::arg("output_key") = "");
+          py::arg("output_key") = "")
+      .def(
+          "image_sharpness",
+          [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_SHARPNESS, factor, output_key));
+          },
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
+      .def(
+          "image_random_sharpness",
+          [wrap](const Self& self, const std::string& key, const py::object& factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_SHARPNESS, enhance_range("image_random_sharpness", factor),
+                                                             output_key));
+          },
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
+      .def(
+          "image_color",
+          [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_COLOR, factor, output_key));
+          },
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
+      .def(
+          "image_random_color",
+          [wrap](const Self& self, const std::string& key, const py::object& factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_COLOR, enhance_range("image_random_color", factor),
+                                                             output_key));
+          },
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
+      .def(
+          "image_brightness",
+          [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_BRIGHTNESS, factor, output_key));
+          },
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
+      .def(
+          "image_random_brightness",
+          [wrap](const Self& self, const std::string& key, const py::object& factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_BRIGHTNESS, enhance_range("image_random_brightness", factor),
+                                                             output_key));
+          },
+          py::arg("key"), py::arg("factor"), py::arg("output_key") = "");
 }
 
 using PadMap = std::unordered_map<std::string, double>;
@@ -856,6 +904,9 @@ PYBIND11_MODULE(_pipeline, m) {
     } else {
       d["warp"] = py::none();
     }
+    // the enhance op: (name, factor)
+    if (p.enhanced) d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor));
+    else d["enhance"] = py::none();
     return d;
   });
 }

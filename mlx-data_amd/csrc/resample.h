@@ -260,6 +260,26 @@ struct WarpRowDev {
 static_assert(sizeof(WarpRowDev) == 112, "WarpRowDev layout");
 // tab_rows: how many entries take the table path; ws: the tables' workspace.
 int launch_warp(const WarpRowDev* rows, int nimgs, int ntiles, int tab_rows, uint8_t* ws, void* stream);
+// The enhance stage (enhance.hip): behind the resize launches (and the warp
+// stage) and before the second pass of an enhance call (mxd_enhance), over u8
+// RGB scratch rows.  One entry per image; a workgroup takes one kEnhTileW x
+// kEnhTileH output tile of one image, tiles numbered through tile_begin.  The
+// stage cannot run in place: src and dst are different rows.
+constexpr int kEnhTileW = 64, kEnhTileH = 16;
+// mxd_enhance_op's values.
+enum EnhanceOp : int32_t { kEnhNone = 0, kEnhSharpness = 1, kEnhColor = 2, kEnhBrightness = 3 };
+struct EnhanceRowDev {
+  const uint8_t* src;  // u8 rows (16-byte aligned base, stride a multiple of 16)
+  uint8_t* dst;        // scratch rows like src, or the caller's u8 destination (any alignment)
+  int64_t src_stride, dst_stride;
+  int32_t w, h;
+  int32_t tile_begin;  // first of the image's workgroups among the launch's
+  int32_t tiles_x;     // tiles per tile row
+  int32_t op;          // EnhanceOp
+  float factor;        // mxd_enhance::factor (0 for MXD_ENHANCE_NONE)
+};
+static_assert(sizeof(EnhanceRowDev) == 56, "EnhanceRowDev layout");
+int launch_enhance(const EnhanceRowDev* rows, int nimgs, int ntiles, void* stream);
 // Waves of this configuration the device runs at once (occupancy x CUs), 0 if unknown.
 int wave_capacity(const WaveCfg& cfg, int device);
 // Diagnostics: the occupancy API's blocks per CU, the kernel's VGPRs and LDS

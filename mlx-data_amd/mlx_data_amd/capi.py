@@ -48,6 +48,8 @@ EXPORTS = (
     "mxd_resize_crop_to_device_tone", "mxd_jpeg_resize_crop_to_device_tone",
     "mxd_warp_validate", "mxd_warp_apply_u8", "mxd_resize_crop_batch_warp", "mxd_resize_crop_to_device_warp",
     "mxd_jpeg_resize_crop_to_device_warp",
+    "mxd_enhance_validate", "mxd_enhance_apply_u8", "mxd_resize_crop_batch_enhance",
+    "mxd_resize_crop_to_device_enhance", "mxd_jpeg_resize_crop_to_device_enhance",
 )
 
 MXD_ELEM_F32 = 0
@@ -461,6 +463,67 @@ def resize_crop_to_device_warp(images, warps, tones, colors, n, out_dtype=MXD_U8
 def jpeg_resize_crop_to_device_warp(images, warps, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
     check(lib().mxd_jpeg_resize_crop_to_device_warp(images, warps, tones, colors, n, out_dtype, _fmt_ref(fmt),
                                                     device))
+
+
+MXD_ENHANCE_NONE = 0
+MXD_ENHANCE_SHARPNESS = 1
+MXD_ENHANCE_COLOR = 2
+MXD_ENHANCE_BRIGHTNESS = 3
+
+
+class MxdEnhance(ctypes.Structure):
+    """struct mxd_enhance (include/mxd_amd.h): an op, its factor, two reserved words (0)."""
+
+    _fields_ = [("op", ctypes.c_int32), ("factor", ctypes.c_float), ("reserved", ctypes.c_int32 * 2)]
+
+
+def make_enhances(enhances):
+    """(op, factor) tuples (or MxdEnhance values) -> ctypes array of mxd_enhance."""
+    arr = (MxdEnhance * max(1, len(enhances)))()
+    for i, e in enumerate(enhances):
+        if isinstance(e, MxdEnhance):
+            arr[i] = e
+            continue
+        arr[i].op = int(e[0])
+        arr[i].factor = float(e[1])
+    return arr
+
+
+def enhance_validate(enhance):
+    """mxd_enhance_validate of one (op, factor) tuple or MxdEnhance."""
+    check(lib().mxd_enhance_validate(make_enhances([enhance])))
+
+
+def enhance_apply_u8(rgb, enhance, out=None):
+    """mxd_enhance_apply_u8: the CPU statement of an enhance op on an (h, w, 3) uint8 image
+    (any row stride); out: an (h, w, 3) uint8 array to write that does not overlap rgb
+    (default: a new one)."""
+    assert rgb.dtype == np.uint8 and rgb.ndim == 3 and rgb.shape[2] == 3 and rgb.strides[1:] == (3, 1)
+    h, w = rgb.shape[:2]
+    if out is None:
+        out = np.empty((h, w, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.shape == rgb.shape and out.strides[1:] == (3, 1)
+    check(lib().mxd_enhance_apply_u8(ctypes.c_void_p(rgb.ctypes.data), w, h, ctypes.c_int64(rgb.strides[0]),
+                                     make_enhances([enhance]), ctypes.c_void_p(out.ctypes.data),
+                                     ctypes.c_int64(out.strides[0])))
+    return out
+
+
+def resize_crop_batch_enhance(images, warps, enhances, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0,
+                              stream=None):
+    check(lib().mxd_resize_crop_batch_enhance(images, warps, enhances, tones, colors, n, out_dtype, _fmt_ref(fmt),
+                                              device, ctypes.c_void_p(stream)))
+
+
+def resize_crop_to_device_enhance(images, warps, enhances, tones, colors, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_resize_crop_to_device_enhance(images, warps, enhances, tones, colors, n, out_dtype,
+                                                  _fmt_ref(fmt), device))
+
+
+def jpeg_resize_crop_to_device_enhance(images, warps, enhances, tones, colors, n, out_dtype=MXD_U8, fmt=None,
+                                       device=0):
+    check(lib().mxd_jpeg_resize_crop_to_device_enhance(images, warps, enhances, tones, colors, n, out_dtype,
+                                                       _fmt_ref(fmt), device))
 
 
 def set_kernel_policy(policy):

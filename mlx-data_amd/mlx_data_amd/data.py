@@ -119,6 +119,27 @@ crop, flip, resize or ``image_rotate`` after a warp, or a warp after a warp,
 tone or colour op, materialises what is pending.  Bad arguments raise
 ``ValueError`` when the op is made.
 
+The enhance ops complete the op set of the PIL augmentation policies (the
+sixth addition): ``image_sharpness(key, factor)``, ``image_color(key, factor)``
+and ``image_brightness(key, factor)`` are Pillow's ``ImageEnhance.Sharpness``,
+``.Color`` and ``.Brightness`` (``Image.blend(degenerate, image, factor)`` with
+the 3 x 3 ``SMOOTH`` filter, the luma grey and black as the degenerate image)
+on the uint8 result, bit for bit; ``ImageEnhance.Contrast`` is
+``image_contrast``.  The random forms ``image_random_sharpness(key,
+factor=(lo, hi))``, ``image_random_color`` and ``image_random_brightness``
+draw one uniform factor per image (a video draws once); all take
+``output_key=""`` and have ``_if`` forms.  Factors are finite and in 0..1e6.
+RGB images only.  The op only marks the pending image and ``batch`` runs it
+in the same call, behind the warp and before the tone op: the stage order is
+geometry, warp, enhance, tone, colour, output form.  Tone and colour ops,
+``image_to_float`` and ``image_normalize`` compose after an enhance op,
+``image_random_h_flip`` composes after all three and a crop after
+``image_color`` / ``image_brightness``; a crop after ``image_sharpness`` (the
+copied outer ring is the uncropped window's), a resize, ``image_rotate``, a
+warp or a second enhance op, or an enhance op after a tone or colour op,
+materialises what is pending.  Bad arguments raise ``ValueError`` when the op
+is made.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole
@@ -181,7 +202,9 @@ def _add_if_variants(cls):
                  "image_color_twist", "image_color_matrix", "image_random_color_twist",
                  "image_posterize", "image_solarize", "image_autocontrast", "image_equalize", "image_contrast",
                  "image_affine", "image_shear", "image_translate", "image_affine_rotate", "image_random_shear",
-                 "image_random_translate", "image_random_affine_rotate"):
+                 "image_random_translate", "image_random_affine_rotate",
+                 "image_sharpness", "image_color", "image_brightness", "image_random_sharpness",
+                 "image_random_color", "image_random_brightness"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 

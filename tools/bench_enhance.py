@@ -1,0 +1,167 @@
+"""What the enhance stage costs and what it saves: per-launch time of the resize
+launch ending in normalised bfloat16 CHW, the same launch with a sharpness or
+a color op per image in front of the format, and the route a user has today.
+
+  python tools/bench_enhance.py [--rounds 3] [--out profiles/r12/enhance_ab.jsonl]
+
+bench.py's method (its C2 and C4 workloads, resident device sets and
+launch_windows: device events around windows of >= 100 launches and >= 20 ms,
+3 per round), every variant warmed first, the variants alternated in one
+process for --rounds rounds (3 rounds: 9 windows each):
+
+  a, a2   mxd_resize_crop_batch_fmt, bfloat16 CHW normalised (twice: the
+          spread between the two is the spread the comparison is held to)
+  b       mxd_resize_crop_batch_enhance, MXD_ENHANCE_SHARPNESS 1.5 for every
+          image, the same format (the stencil path of enhance_rows)
+  c       as b with MXD_ENHANCE_COLOR 1.5 (the pointwise path)
+  n       as b with MXD_ENHANCE_NONE (the stage as a copy: its fixed cost)
+  d       what a user runs today: the u8 mxd_resize_crop_batch, then torch on
+          the same stream -- depthwise conv2d with the / 13 kernel, the ring
+          copy, the blend, truncate, clamp, / 255, normalise, permute and cast
+          to bfloat16
+
+--variants picks a subset (a profiler run of the enhance call alone: --variants b).
+--lib times another build of the library: enhance.hip compiled with
+-DMXD_ENH_LDS stages the tile and its halo in LDS instead of reading the
+stencil's neighbours straight from the rows (DESIGN.md section 5k has both rows).
+
+One JSON line per (workload, variant): median ms per launch over every window
+of every round, min, max, the windows; then one summary line per workload."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "mlx-data_amd"))
+
+import bench  # noqa: E402
+
+MEAN = (0.485, 0.456, 0.406)
+STD = (0.229, 0.224, 0.225)
+FACTOR = 1.5
+
+
+def run_workload(name, capi, torch, rounds, emit, only):
+    import torch.nn.functional as F
+
+    dev = 0
+    L = capi.lib()
+    B = bench.WORKLOADS[name]["batch"]
+    sizes, geoms, _ = bench.make_workload(capi, name, B, 0)
+    C, cw, ch = bench.C, 224, 224
+    assert all(g[4] == cw and g[5] == ch for g in geoms)
+    stream = capi.Stream(dev)
+    hs = ctypes.c_void_p(stream.handle)
+    sets, _ = bench.device_sets(capi, dev, sizes, geoms, False, 2, 3000)
+    ext = torch.cuda.ExternalStream(stream.handle, device=torch.device("cuda:0"))
+    u8s = [torch.empty((B, ch, cw, C), dtype=torch.uint8, device="cuda:0") for _ in sets]
+    outs = [torch.empty((B, C, ch, cw), dtype=torch.bfloat16, device="cuda:0") for _ in sets]
+    arrays = {"u8": [], "chw16": []}
+    for (src, dst, imgs, n), x, y in zip(sets, u8s, outs):
+        for kind in arrays:
+            arr = (capi.MxdImage * n)()
+            ctypes.memmove(arr, imgs, ctypes.sizeof(arr))
+            for i in range(n):
+                arr[i].dst = x.data_ptr() + i * ch * cw * C if kind == "u8" else y.data_ptr() + i * C * ch * cw * 2
+                arr[i].dst_stride = cw * C if kind == "u8" else cw * 2
+            arrays[kind].append(arr)
+    fmt = capi.make_out_format(capi.MXD_ELEM_BF16, capi.MXD_LAYOUT_CHW, MEAN, STD, plane_stride=ch * cw * 2)
+    sharp = capi.make_enhances([(capi.MXD_ENHANCE_SHARPNESS, FACTOR)] * B)
+    color = capi.make_enhances([(capi.MXD_ENHANCE_COLOR, FACTOR)] * B)
+    none = capi.make_enhances([(capi.MXD_ENHANCE_NONE, 0.0)] * B)
+    smooth = torch.tensor([[1.0, 1.0, 1.0], [1.0, 5.0, 1.0], [1.0, 1.0, 1.0]], device="cuda:0") / 13.0
+    smooth = smooth.view(1, 1, 3, 3).expand(C, 1, 3, 3).contiguous()
+    mean_t = torch.tensor(MEAN, device="cuda:0").view(1, 3, 1, 1)
+    std_t = torch.tensor(STD, device="cuda:0").view(1, 3, 1, 1)
+
+    def call(rc):
+        if rc != 0:
+            raise RuntimeError(L.mxd_last_error().decode())
+
+    def a(i):
+        call(L.mxd_resize_crop_batch_fmt(arrays["chw16"][i % 2], B, ctypes.byref(fmt), dev, hs))
+
+    def enhance_call(enhs):
+        def f(i):
+            call(L.mxd_resize_crop_batch_enhance(arrays["chw16"][i % 2], None, enhs, None, None, B, capi.MXD_U8,
+                                                 ctypes.byref(fmt), dev, hs))
+        return f
+
+    def d(i):
+        call(L.mxd_resize_crop_batch(arrays["u8"][i % 2], B, capi.MXD_U8, dev, hs))
+        with torch.cuda.stream(ext):
+            x = u8s[i % 2].permute(0, 3, 1, 2).float()
+            deg = x.clone()
+            deg[:, :, 1:-1, 1:-1] = torch.floor(F.conv2d(x, smooth, groups=C) + 0.5)
+            y = torch.clamp(torch.trunc(deg + FACTOR * (x - deg)), 0, 255)
+            ((y / 255 - mean_t) / std_t).to(torch.bfloat16)
+
+    every = {"a": a, "b": enhance_call(sharp), "c": enhance_call(color), "n": enhance_call(none), "d": d, "a2": a}
+    variants = {k: f for k, f in every.items() if not only or k in only}
+    try:
+        for f in variants.values():  # every shape and variant warmed first
+            for i in range(10):
+                f(i)
+        stream.synchronize()
+        windows = {k: [] for k in variants}
+        for _ in range(rounds):
+            for k, f in variants.items():
+                windows[k] += bench.launch_windows(capi, stream, f, stream.synchronize)[2]
+        med = {}
+        for k, w in windows.items():
+            med[k] = statistics.median(w)
+            emit({"workload": name, "variant": k, "images": B, "ms_per_launch": round(med[k], 5), "min": min(w),
+                  "max": max(w), "windows": w})
+        if not only:
+            lo = min(med["a"], med["a2"])
+            emit({"workload": name, "summary": True, "b_over_a": round(med["b"] / lo, 4), "c_over_a": round(med["c"] / lo, 4),
+                  "n_over_a": round(med["n"] / lo, 4), "d_over_b": round(med["d"] / med["b"], 2),
+                  "d_over_c": round(med["d"] / med["c"], 2), "a_spread": round(abs(med["a"] - med["a2"]) / lo, 4)})
+    finally:
+        stream.synchronize()
+        for src, dst, _, _ in sets:
+            src.free()
+            dst.free()
+        stream.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--workloads", default="c2,c4")
+    ap.add_argument("--variants", default="")
+    ap.add_argument("--out", default="")
+    ap.add_argument("--lib", default="", help="another build of libmxd_amd.so to time (a compile-time variant)")
+    args = ap.parse_args()
+    import torch  # torch first: its HIP runtime is the one the libraries bind
+
+    torch.zeros(1, device="cuda:0")
+    from mlx_data_amd import capi
+
+    if args.lib:
+        capi.LIB_PATH = os.path.abspath(args.lib)
+    capi.check(capi.lib().mxd_set_device(0))
+    out = open(args.out, "a") if args.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    name, arch, cus = capi.device_properties(0)
+    emit({"device": name, "arch": arch, "cus": cus, "rounds": args.rounds, "torch": torch.__version__,
+          "lib": os.path.basename(args.lib) if args.lib else "product",
+          "method": "bench.launch_windows: device events, windows >= 100 launches and >= 20 ms, 3 per round"})
+    only = set(args.variants.split(",")) if args.variants else set()
+    for wl in args.workloads.split(","):
+        run_workload(wl, capi, torch, args.rounds, emit, only)
+
+
+if __name__ == "__main__":
+    main()
