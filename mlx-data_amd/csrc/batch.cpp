@@ -405,42 +405,34 @@ int launch_all(const BatchLayout& L, const ImgDev* dev, Workspace* ws, const mxd
   return launch_rc;
 }
 
-// The second pass of the layout's kind over its entries in the uploaded copy.
-int launch_second_pass(const BatchLayout& L, const ImgDev* dev, const mxd::OutFmtDev& ofd, void* stream) {
-  if (L.fmt_count == 0) return MXD_OK;
-  const void* entries = dev + L.fmt_at;
+// One stage of the chain over its entries in the uploaded copy.
+int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDev* dev, const mxd::OutFmtDev& ofd,
+                 void* stream) {
+  if (st.count == 0) return MXD_OK;  // (a formatted call whose every image a wave kernel took)
+  const void* entries = dev + st.at;
   const char* what = "format_rows launch failed: ";
   int rc = 0;
-  if (L.pass == SecondPass::Tone) {
+  if (st.kind == StageKind::Warp) {
+    what = "warp launch failed: ";
+    rc = mxd::launch_warp(static_cast<const mxd::WarpRowDev*>(entries), st.count, st.blocks, st.pre_blocks, L.warp_tab, stream);
+  } else if (st.kind == StageKind::Enhance) {
+    what = "enhance launch failed: ";
+    rc = mxd::launch_enhance(static_cast<const mxd::EnhanceRowDev*>(entries), st.count, st.blocks, stream);
+  } else if (L.pass == SecondPass::Tone) {
     // this call's statistics start from zero, whatever the stream's last call left
     if (L.tone_stat_bytes > 0 &&
         hipMemsetAsync(L.tone_ws, 0, L.tone_stat_bytes, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
       return fail(MXD_ERR_DEVICE, std::string("tone workspace memset failed: ") + hipGetErrorString(hipGetLastError()));
     what = "tone launch failed: ";
-    rc = mxd::launch_tone(static_cast<const mxd::ToneRowDev*>(entries), L.fmt_count, L.tone_hist_blocks, L.fmt_blocks, ofd,
-                          L.tone_ws, L.matrix, stream);
+    rc = mxd::launch_tone(static_cast<const mxd::ToneRowDev*>(entries), st.count, st.pre_blocks, st.blocks, ofd, L.tone_ws,
+                          L.matrix, stream);
   } else if (L.pass == SecondPass::Color) {
     what = "color_rows launch failed: ";
-    rc = mxd::launch_color_rows(static_cast<const mxd::ColorRowDev*>(entries), L.fmt_count, L.fmt_blocks, ofd, stream);
+    rc = mxd::launch_color_rows(static_cast<const mxd::ColorRowDev*>(entries), st.count, st.blocks, ofd, stream);
   } else {
-    rc = mxd::launch_format_rows(static_cast<const mxd::FmtRowDev*>(entries), L.fmt_count, L.fmt_blocks, ofd, stream);
+    rc = mxd::launch_format_rows(static_cast<const mxd::FmtRowDev*>(entries), st.count, st.blocks, ofd, stream);
   }
   if (rc) return fail(MXD_ERR_DEVICE, std::string(what) + hipGetErrorString(hipGetLastError()));
-  return MXD_OK;
-}
-
-// The warp stage of a warp call: between the resize kernels and the second pass.
-int launch_warp_stage(const BatchLayout& L, const ImgDev* dev, void* stream) {
-  if (mxd::launch_warp(reinterpret_cast<const mxd::WarpRowDev*>(dev + L.warp_at), L.n, L.warp_tiles, L.warp_tab_count,
-                       L.warp_tab, stream))
-    return fail(MXD_ERR_DEVICE, std::string("warp launch failed: ") + hipGetErrorString(hipGetLastError()));
-  return MXD_OK;
-}
-
-// The enhance stage of an enhance call: behind the warp stage, before the second pass.
-int launch_enhance_stage(const BatchLayout& L, const ImgDev* dev, void* stream) {
-  if (mxd::launch_enhance(reinterpret_cast<const mxd::EnhanceRowDev*>(dev + L.enhance_at), L.n, L.enhance_tiles, stream))
-    return fail(MXD_ERR_DEVICE, std::string("enhance launch failed: ") + hipGetErrorString(hipGetLastError()));
   return MXD_OK;
 }
 
@@ -460,11 +452,9 @@ int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_
   bool hit = false;
   if (int rc = upload_descs(L.descs, device, stream, &dev, &hold, &ws, &hit)) return rc;
   int launch_rc = launch_all(L, dev, ws, ops.resize_formats() ? &ofd : nullptr, stream);
-  // The second pass, behind the joins: every resize kernel that wrote scratch
-  // rows is ordered before it on the caller's stream.
-  if (launch_rc == MXD_OK && L.warped) launch_rc = launch_warp_stage(L, dev, stream);
-  if (launch_rc == MXD_OK && L.enhanced) launch_rc = launch_enhance_stage(L, dev, stream);
-  if (launch_rc == MXD_OK) launch_rc = launch_second_pass(L, dev, ofd, stream);
+  // The chain, behind the joins: every resize kernel that wrote scratch rows
+  // is ordered before it on the caller's stream.
+  for (int32_t s = 0; s < L.nstages && launch_rc == MXD_OK; s++) launch_rc = launch_stage(L, L.chain[s], dev, ofd, stream);
   // The batch is counted on a failed launch too (see launch_all).
   const int rel = release_descs(ws, stream, hit);
   return launch_rc != MXD_OK ? launch_rc : rel;

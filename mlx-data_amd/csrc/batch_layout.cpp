@@ -338,61 +338,60 @@ void place_scratch(Batch& b, const mxd_image* callers) {
   b.L.scratch_bytes = at;
 }
 
-// The head of an entry: scratch rows `im` to the caller's destination.
-mxd::FmtRowDev entry_head(const mxd_image& im, const mxd_image& caller, int32_t blk_begin) {
-  return mxd::FmtRowDev{static_cast<const uint8_t*>(im.dst), caller.dst, im.dst_stride, caller.dst_stride,
-                        im.crop_w, im.crop_h, im.channels, blk_begin};
+// The chain of a call (the rule: capi_internal.h, above PostOps): which
+// stages follow the resize, and which rows each reads and writes.
+void derive_chain(const PostOps& ops, BatchLayout& L) {
+  L.pass = ops.pass();
+  if (ops.warps) L.chain[L.nstages++].kind = StageKind::Warp;
+  if (ops.enhances) L.chain[L.nstages++].kind = StageKind::Enhance;
+  if (L.pass != SecondPass::None) L.chain[L.nstages++].kind = StageKind::Pass;
+  for (int32_t s = 0; s < L.nstages; s++) {
+    BatchLayout::Stage& st = L.chain[s];
+    st.reads = s % 2 ? Rows::B : Rows::A;
+    st.writes = s == L.nstages - 1 ? Rows::Dst : s % 2 ? Rows::A : Rows::B;
+    st.entry_size = st.kind == StageKind::Warp       ? sizeof(mxd::WarpRowDev)
+                    : st.kind == StageKind::Enhance  ? sizeof(mxd::EnhanceRowDev)
+                    : L.pass == SecondPass::Tone     ? sizeof(mxd::ToneRowDev)
+                    : L.pass == SecondPass::Color    ? sizeof(mxd::ColorRowDev)
+                                                     : sizeof(mxd::FmtRowDev);
+  }
 }
 
 // Whether a warp takes the table path: Pillow's scale path of NEAREST.
 bool warp_tabled(const mxd_warp& w) { return w.mode == MXD_WARP_NEAREST && w.m[1] == 0.0 && w.m[3] == 0.0; }
+size_t warp_tab_size(const mxd_image& im) { return (((size_t)im.crop_w + im.crop_h) * 4 + 15) & ~(size_t)15; }
 
-// A warp or enhance call's scratch behind the rows A the resize kernels
-// write: rows B when a second pass or the enhance stage follows the first
-// stage, then a warp call's index tables.
-void place_warp_scratch(Batch& b, const PostOps& ops) {
+// A stage's entries at the end of the upload (zeroed), their heads written:
+// one per image the stage reads, in batch order.
+void append_stage(Batch& b, const mxd_image* callers, BatchLayout::Stage& st) {
   BatchLayout& L = b.L;
-  if (L.pass != SecondPass::None || (L.warped && L.enhanced)) {
-    L.warp_b_at = (L.scratch_bytes + 255) & ~(size_t)255;
-    L.scratch_bytes = L.warp_b_at + L.scratch_bytes;
+  const bool every = st.kind != StageKind::Pass;
+  for (int32_t i = 0; i < b.n; i++) st.count += every || second_pass_reads(b, i) ? 1 : 0;
+  st.at = L.descs.size();
+  L.descs.resize(st.at + ((size_t)st.count * st.entry_size + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+  for (int32_t i = 0, j = 0; i < b.n; i++) {
+    if (!every && !second_pass_reads(b, i)) continue;
+    const mxd_image& im = L.images[i];
+    const bool out = st.writes == Rows::Dst;
+    const mxd::RowHead h{static_cast<const uint8_t*>(im.dst) + (st.reads == Rows::B ? L.b_at : 0),
+                         out ? callers[i].dst : static_cast<uint8_t*>(im.dst) + (st.writes == Rows::B ? L.b_at : 0),
+                         im.dst_stride, out ? callers[i].dst_stride : im.dst_stride, im.crop_w, im.crop_h};
+    std::memcpy(L.head(st, j++), &h, sizeof h);
   }
-  if (!L.warped) return;
-  L.warp_tab_at = (L.scratch_bytes + 255) & ~(size_t)255;
-  size_t tab_bytes = 0;
-  for (int32_t i = 0; i < b.n; i++)
-    if (warp_tabled(ops.warps[i])) {
-      L.warp_tab_count++;
-      tab_bytes += (((size_t)L.images[i].crop_w + L.images[i].crop_h) * 4 + 15) & ~(size_t)15;
-    }
-  if (tab_bytes > 0) L.scratch_bytes = L.warp_tab_at + tab_bytes;
 }
 
-// The warp stage's entries, in batch order, behind everything else of the
-// upload: modes, fills and matrices are part of its bytes, so a cached slot is
-// reused only for the same ones.
-void append_warps(Batch& b, const mxd_image* callers, const PostOps& ops) {
+// The warp stage's own fields: modes, fills and matrices are part of the
+// upload's bytes, so a cached slot is reused only for the same ones.
+void fill_warps(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
   BatchLayout& L = b.L;
-  L.warp_at = L.descs.size();
-  L.descs.resize(L.warp_at + ((size_t)b.n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
   size_t tab_at = L.warp_tab_at;
-  int32_t tabs = 0;
   for (int32_t i = 0; i < b.n; i++) {
     const mxd_image& im = L.images[i];
     const mxd_warp& wp = ops.warps[i];
     mxd::WarpRowDev& e = L.warp_entry(i);
-    e.src = static_cast<const uint8_t*>(im.dst);
-    e.src_stride = im.dst_stride;
-    if (L.pass != SecondPass::None || L.enhanced) {
-      e.dst = static_cast<uint8_t*>(im.dst) + L.warp_b_at;
-      e.dst_stride = im.dst_stride;
-    } else {
-      e.dst = static_cast<uint8_t*>(callers[i].dst);
-      e.dst_stride = callers[i].dst_stride;
-    }
-    e.w = im.crop_w, e.h = im.crop_h;
-    e.tile_begin = L.warp_tiles;
+    e.tile_begin = st.blocks;
     e.tiles_x = (im.crop_w + mxd::kWarpTileW - 1) / mxd::kWarpTileW;
-    L.warp_tiles += e.tiles_x * ((im.crop_h + mxd::kWarpTileH - 1) / mxd::kWarpTileH);
+    st.blocks += e.tiles_x * ((im.crop_h + mxd::kWarpTileH - 1) / mxd::kWarpTileH);
     e.path = wp.mode == MXD_WARP_NONE       ? mxd::kWarpCopy
              : warp_tabled(wp)              ? mxd::kWarpTable
              : wp.mode == MXD_WARP_NEAREST  ? mxd::kWarpFixed
@@ -401,39 +400,25 @@ void append_warps(Batch& b, const mxd_image* callers, const PostOps& ops) {
     e.tab_off = 0, e.tab_index = -1;
     if (e.path == mxd::kWarpTable) {
       e.tab_off = (int32_t)(tab_at - L.warp_tab_at);
-      e.tab_index = tabs++;
-      tab_at += (((size_t)im.crop_w + im.crop_h) * 4 + 15) & ~(size_t)15;
+      e.tab_index = st.pre_blocks++;
+      tab_at += warp_tab_size(im);
     }
     // (MXD_WARP_NONE reads nothing of the matrix: zeros, so equal calls make equal bytes)
     for (int k = 0; k < 6; k++) e.m[k] = e.path == mxd::kWarpCopy ? 0.0 : wp.m[k];
   }
 }
 
-// The enhance stage's entries, in batch order, behind the warp stage's: ops
-// and factors are part of its bytes, so a cached slot is reused only for the
-// same ones.  It reads what the stage before it wrote (rows A, or the warp's
-// rows B) and writes the other rows, or the destinations when nothing follows.
-void append_enhances(Batch& b, const mxd_image* callers, const PostOps& ops) {
+// The enhance stage's own fields: ops and factors are part of the upload's
+// bytes, so a cached slot is reused only for the same ones.
+void fill_enhances(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
   BatchLayout& L = b.L;
-  L.enhance_at = L.descs.size();
-  L.descs.resize(L.enhance_at + ((size_t)b.n * sizeof(mxd::EnhanceRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
   for (int32_t i = 0; i < b.n; i++) {
     const mxd_image& im = L.images[i];
     const mxd_enhance& en = ops.enhances[i];
     mxd::EnhanceRowDev& e = L.enhance_entry(i);
-    e.src = static_cast<const uint8_t*>(im.dst) + (L.warped ? L.warp_b_at : 0);
-    e.src_stride = im.dst_stride;
-    if (L.pass != SecondPass::None) {
-      e.dst = static_cast<uint8_t*>(im.dst) + (L.warped ? 0 : L.warp_b_at);
-      e.dst_stride = im.dst_stride;
-    } else {
-      e.dst = static_cast<uint8_t*>(callers[i].dst);
-      e.dst_stride = callers[i].dst_stride;
-    }
-    e.w = im.crop_w, e.h = im.crop_h;
-    e.tile_begin = L.enhance_tiles;
+    e.tile_begin = st.blocks;
     e.tiles_x = (im.crop_w + mxd::kEnhTileW - 1) / mxd::kEnhTileW;
-    L.enhance_tiles += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
+    st.blocks += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
     e.op = en.op;
     // (MXD_ENHANCE_NONE reads no factor: zero, so equal calls make equal bytes)
     e.factor = en.op == MXD_ENHANCE_NONE ? 0.0f : en.factor;
@@ -442,10 +427,8 @@ void append_enhances(Batch& b, const mxd_image* callers, const PostOps& ops) {
 
 // After every descriptor, in ImgDev-sized blocks: the unit -> image tables of
 // the band launches whose images differ in unit count (int32 each), then the
-// second pass's entries: part of the upload's bytes, so a cached slot is
-// reused only with the same scratch rows and destinations (and matrices, ops
-// and parameters).
-void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
+// stages' entries (append_stages).
+void append_tables(Batch& b) {
   BatchLayout& L = b.L;
   std::vector<int32_t> unit_tables;
   for (BatchLayout::BandGroup& g : L.bands) {
@@ -462,20 +445,22 @@ void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
   if (!unit_tables.empty())
     std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.tables_at), unit_tables.data(), unit_tables.size() * 4);
   L.fmt_at = L.descs.size();
-  if (L.warped || L.enhanced) place_warp_scratch(b, ops);
-  if (L.pass == SecondPass::None) return;
-  for (int32_t i = 0; i < b.n; i++) L.fmt_count += second_pass_reads(b, i) ? 1 : 0;
-  L.descs.resize(L.fmt_at + ((size_t)L.fmt_count * L.entry_size + sizeof(ImgDev) - 1) / sizeof(ImgDev));  // (zeroed)
+}
+
+// The second pass's own fields (matrices, ops and parameters: part of the
+// upload's bytes like the rows), and a tone call's workspace behind
+// everything else of the scratch: statistics first.
+void fill_second_pass(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
+  BatchLayout& L = b.L;
   const int32_t block_rows = L.pass == SecondPass::Format ? mxd::kFmtRows : mxd::kPixelRows;
   int32_t stats = 0;
   for (int32_t i = 0, j = 0; i < b.n; i++) {
     if (!second_pass_reads(b, i)) continue;
     const mxd_image& im = L.images[i];
     mxd::FmtRowDev& head = L.entry(j++);
-    head = entry_head(im, callers[i], L.fmt_blocks);
-    // (a warp or an enhance call: the stage's rows B; both: the enhance stage's, A again)
-    if (!(L.warped && L.enhanced)) head.src += L.warp_b_at;
-    L.fmt_blocks += (im.crop_h + block_rows - 1) / block_rows;
+    head.channels = im.channels;
+    head.blk_begin = st.blocks;
+    st.blocks += (im.crop_h + block_rows - 1) / block_rows;
     if (L.pass == SecondPass::Format) continue;
     mxd::ColorRowDev& c = reinterpret_cast<mxd::ColorRowDev&>(head);
     for (int k = 0; k < 12; k++) c.m[k] = ops.colors ? color_entry(ops.colors[i].m[k / 4][k % 4]) : k % 5 == 0 ? 1.0f : 0.0f;
@@ -483,12 +468,12 @@ void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
     // The workspace follows the scratch rows: statistics first.
     mxd::ToneRowDev& t = reinterpret_cast<mxd::ToneRowDev&>(head);
     t.op = ops.tones[i].op, t.arg = ops.tones[i].arg, t.factor = ops.tones[i].factor;
-    t.hist_begin = L.tone_hist_blocks;
+    t.hist_begin = st.pre_blocks;
     t.stat_off = -1;
     if (mxd::tone_needs_stats(t.op)) {
       t.stat_off = stats * (int32_t)(mxd::kToneStatWords * sizeof(uint32_t));
       stats++;
-      L.tone_hist_blocks += (im.crop_h + mxd::kToneHistRows - 1) / mxd::kToneHistRows;
+      st.pre_blocks += (im.crop_h + mxd::kToneHistRows - 1) / mxd::kToneHistRows;
     }
   }
   if (L.pass != SecondPass::Tone) return;
@@ -497,6 +482,30 @@ void append_tables(Batch& b, const mxd_image* callers, const PostOps& ops) {
     reinterpret_cast<mxd::ToneRowDev&>(L.entry(i)).lut_off = (int32_t)(L.tone_stat_bytes + (size_t)i * mxd::kToneLutBytes);
   L.tone_ws_at = (L.scratch_bytes + 255) & ~(size_t)255;
   L.scratch_bytes = L.tone_ws_at + L.tone_stat_bytes + (size_t)b.n * mxd::kToneLutBytes;
+}
+
+// The chain's scratch behind rows A, then its entries behind the tables: the
+// second pass's first, then the warp stage's, then the enhance stage's.
+void append_stages(Batch& b, const mxd_image* callers, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  if (L.nstages >= 2) {
+    L.b_at = (L.scratch_bytes + 255) & ~(size_t)255;
+    L.scratch_bytes = L.b_at + L.scratch_bytes;
+  }
+  if (ops.warps) {
+    L.warp_tab_at = (L.scratch_bytes + 255) & ~(size_t)255;
+    size_t tab_bytes = 0;
+    for (int32_t i = 0; i < b.n; i++) tab_bytes += warp_tabled(ops.warps[i]) ? warp_tab_size(L.images[i]) : 0;
+    if (tab_bytes > 0) L.scratch_bytes = L.warp_tab_at + tab_bytes;
+  }
+  for (StageKind kind : {StageKind::Pass, StageKind::Warp, StageKind::Enhance}) {
+    BatchLayout::Stage* st = L.stage(kind);
+    if (!st) continue;
+    append_stage(b, callers, *st);
+    if (kind == StageKind::Pass) fill_second_pass(b, *st, ops);
+    if (kind == StageKind::Warp) fill_warps(b, *st, ops);
+    if (kind == StageKind::Enhance) fill_enhances(b, *st, ops);
+  }
 }
 
 }  // namespace
@@ -509,22 +518,16 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity) {
 void BatchLayout::add_scratch(uint8_t* base) {
   for (int32_t k = 0; k < n; k++)
     if (pass != SecondPass::Format || !plans[image_of[k]].wave) descs[k].dst = base + reinterpret_cast<uintptr_t>(descs[k].dst);
-  for (int32_t j = 0; j < fmt_count; j++) entry(j).src = base + reinterpret_cast<uintptr_t>(entry(j).src);
+  for (int32_t s = 0; s < nstages; s++)
+    for (int32_t j = 0; j < chain[s].count; j++) {
+      mxd::RowHead h;
+      std::memcpy(&h, head(chain[s], j), sizeof h);
+      h.src = base + reinterpret_cast<uintptr_t>(h.src);
+      if (chain[s].writes != Rows::Dst) h.dst = base + reinterpret_cast<uintptr_t>(h.dst);
+      std::memcpy(head(chain[s], j), &h, sizeof h);
+    }
   if (pass == SecondPass::Tone) tone_ws = base + tone_ws_at;
-  if (warped) {
-    for (int32_t i = 0; i < n; i++) {
-      mxd::WarpRowDev& e = warp_entry(i);
-      e.src = base + reinterpret_cast<uintptr_t>(e.src);
-      if (pass != SecondPass::None || enhanced) e.dst = base + reinterpret_cast<uintptr_t>(e.dst);
-    }
-    warp_tab = base + warp_tab_at;
-  }
-  if (enhanced)
-    for (int32_t i = 0; i < n; i++) {
-      mxd::EnhanceRowDev& e = enhance_entry(i);
-      e.src = base + reinterpret_cast<uintptr_t>(e.src);
-      if (pass != SecondPass::None) e.dst = base + reinterpret_cast<uintptr_t>(e.dst);
-    }
+  if (warped()) warp_tab = base + warp_tab_at;
 }
 
 int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, int32_t n, const Stored* stored,
@@ -532,14 +535,8 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   *out = BatchLayout{};
   BatchLayout& L = *out;
   L.n = n;
-  L.pass = ops.pass();
-  L.entry_size = L.pass == SecondPass::Tone    ? sizeof(mxd::ToneRowDev)
-                 : L.pass == SecondPass::Color ? sizeof(mxd::ColorRowDev)
-                 : L.pass == SecondPass::Format ? sizeof(mxd::FmtRowDev)
-                                                : 0;
+  derive_chain(ops, L);
   L.matrix = ops.colors != nullptr;
-  L.warped = ops.warps != nullptr;
-  L.enhanced = ops.enhances != nullptr;
   // A formatted call plans its kernels as a u8 call does: the wave kernels
   // exist in the same shapes in every output mode and write any element
   // alignment, and an image they do not take is resized into u8 scratch rows
@@ -567,9 +564,8 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = band_groups(b)) return rc;
   if (int rc = wave_groups(b)) return rc;
   if (int rc = general_group(b)) return rc;
-  append_tables(b, callers, ops);
-  if (L.warped) append_warps(b, callers, ops);
-  if (L.enhanced) append_enhances(b, callers, ops);
+  append_tables(b);
+  append_stages(b, callers, ops);
   // Largest first (a band unit is a workgroup, ~4 wave units).
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});

@@ -161,36 +161,14 @@ int run_pixmap(const mxd_pixmap* images, int32_t n, int32_t op, int32_t device, 
 
 using namespace mxd::capi;
 
-// The head of the _color (tones == nullptr, tone_call false) and _tone entry
-// points: the format when there is one, the call's own array; an empty call
-// keeps the format alone.
-static int post_ops(const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones, bool tone_call, int32_t n,
-                    PostOps* ops) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !tone_call && !colors) return fail(MXD_ERR_INVALID, "mxd: null colors");
-  if (n > 0 && tone_call && !tones) return fail(MXD_ERR_INVALID, "mxd: null tones");
-  *ops = n > 0 ? PostOps{fmt, colors, tones} : PostOps{fmt};
-  return MXD_OK;
-}
-
-// The head of the _warp entry points: warps required, everything else optional.
-static int warp_ops(const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones, const mxd_warp* warps,
-                    int32_t n, PostOps* ops) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !warps) return fail(MXD_ERR_INVALID, "mxd: null warps");
-  *ops = n > 0 ? PostOps{fmt, colors, tones, warps} : PostOps{fmt};
-  return MXD_OK;
-}
-
-// The head of the _enhance entry points: enhances required, everything else optional.
-static int enhance_ops(const mxd_out_format* fmt, const mxd_color* colors, const mxd_tone* tones, const mxd_warp* warps,
-                       const mxd_enhance* enhances, int32_t n, PostOps* ops) {
-  if (fmt)
-    if (int rc = fmt_validate(fmt, 0)) return rc;
-  if (n > 0 && !enhances) return fail(MXD_ERR_INVALID, "mxd: null enhances");
-  *ops = n > 0 ? PostOps{fmt, colors, tones, warps, enhances} : PostOps{fmt};
+// The head of the _color, _tone, _warp and _enhance entry points: the format
+// when there is one, the call's own array (`required`, named `what`) present,
+// every other member optional; an empty call keeps the format alone.
+static int post_ops(PostOps given, const void* required, const char* what, int32_t n, PostOps* ops) {
+  if (given.fmt)
+    if (int rc = fmt_validate(given.fmt, 0)) return rc;
+  if (n > 0 && !required) return fail(MXD_ERR_INVALID, std::string("mxd: null ") + what);
+  *ops = n > 0 ? given : PostOps{given.fmt};
   return MXD_OK;
 }
 
@@ -287,14 +265,14 @@ int mxd_resize_crop_batch_fmt(const mxd_image* images, int32_t n, const mxd_out_
 int mxd_resize_crop_batch_color(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t out_dtype,
                                 const mxd_out_format* fmt, int32_t device, void* stream) {
   PostOps ops;
-  if (int rc = post_ops(fmt, colors, nullptr, false, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors}, colors, "colors", n, &ops)) return rc;
   return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
 int mxd_resize_crop_batch_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
                                int32_t out_dtype, const mxd_out_format* fmt, int32_t device, void* stream) {
   PostOps ops;
-  if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones}, tones, "tones", n, &ops)) return rc;
   return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
@@ -302,7 +280,7 @@ int mxd_resize_crop_batch_warp(const mxd_image* images, const mxd_warp* warps, c
                                const mxd_color* colors, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
                                int32_t device, void* stream) {
   PostOps ops;
-  if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones, warps}, warps, "warps", n, &ops)) return rc;
   return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
@@ -310,7 +288,7 @@ int mxd_resize_crop_batch_enhance(const mxd_image* images, const mxd_warp* warps
                                   const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t out_dtype,
                                   const mxd_out_format* fmt, int32_t device, void* stream) {
   PostOps ops;
-  if (int rc = enhance_ops(fmt, colors, tones, warps, enhances, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones, warps, enhances}, enhances, "enhances", n, &ops)) return rc;
   return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
@@ -507,14 +485,14 @@ int mxd_resize_crop_to_device(const mxd_image* images, int32_t n, int32_t out_dt
 int mxd_resize_crop_to_device_color(const mxd_image* images, const mxd_color* colors, int32_t n, int32_t out_dtype,
                                     const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
-  if (int rc = post_ops(fmt, colors, nullptr, false, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors}, colors, "colors", n, &ops)) return rc;
   return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
 int mxd_resize_crop_to_device_tone(const mxd_image* images, const mxd_tone* tones, const mxd_color* colors, int32_t n,
                                    int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
-  if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones}, tones, "tones", n, &ops)) return rc;
   return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
@@ -522,7 +500,7 @@ int mxd_resize_crop_to_device_warp(const mxd_image* images, const mxd_warp* warp
                                    const mxd_color* colors, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
                                    int32_t device) {
   PostOps ops;
-  if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones, warps}, warps, "warps", n, &ops)) return rc;
   return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
@@ -530,7 +508,7 @@ int mxd_resize_crop_to_device_enhance(const mxd_image* images, const mxd_warp* w
                                       const mxd_tone* tones, const mxd_color* colors, int32_t n, int32_t out_dtype,
                                       const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
-  if (int rc = enhance_ops(fmt, colors, tones, warps, enhances, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones, warps, enhances}, enhances, "enhances", n, &ops)) return rc;
   return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
@@ -633,14 +611,14 @@ int mxd_jpeg_resize_crop_to_device(const mxd_jpeg_image* images, int32_t n, int3
 int mxd_jpeg_resize_crop_to_device_color(const mxd_jpeg_image* images, const mxd_color* colors, int32_t n,
                                          int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
-  if (int rc = post_ops(fmt, colors, nullptr, false, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors}, colors, "colors", n, &ops)) return rc;
   return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 
 int mxd_jpeg_resize_crop_to_device_tone(const mxd_jpeg_image* images, const mxd_tone* tones, const mxd_color* colors,
                                         int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
-  if (int rc = post_ops(fmt, colors, tones, true, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones}, tones, "tones", n, &ops)) return rc;
   return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 
@@ -648,7 +626,7 @@ int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_
                                         const mxd_color* colors, int32_t n, int32_t out_dtype,
                                         const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
-  if (int rc = warp_ops(fmt, colors, tones, warps, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones, warps}, warps, "warps", n, &ops)) return rc;
   return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 
@@ -656,7 +634,7 @@ int mxd_jpeg_resize_crop_to_device_enhance(const mxd_jpeg_image* images, const m
                                            const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
                                            int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
-  if (int rc = enhance_ops(fmt, colors, tones, warps, enhances, n, &ops)) return rc;
+  if (int rc = post_ops({fmt, colors, tones, warps, enhances}, enhances, "enhances", n, &ops)) return rc;
   return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 

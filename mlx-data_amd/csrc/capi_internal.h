@@ -269,18 +269,21 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
 // warps[i] belongs to images[i]; every other member may be null then.
 // enhances: an enhance call, enhances[i] belongs to images[i]; every other
 // member may be null then.
-// The second pass (row_stage.hip) such a call launches behind its resize
-// kernels: format_rows for the images of a formatted call that no wave kernel
-// takes, pixel_rows for every image of a colour or tone call.  A warp call
-// resizes every image into scratch rows A in u8 and runs the warp stage
-// (warp.hip) in front of the second pass, which then reads every image (a
-// format alone: through pixel_rows with identity matrices) from the warp's
-// scratch rows B; with no second pass the warp stage writes the u8
-// destinations itself.  An enhance call runs the enhance stage (enhance.hip)
-// behind the warp stage, if any: it reads A and writes B without a warp, reads
-// B and writes A (dead by then) with one, or the u8 destinations when no
-// second pass follows; the second pass reads the rows the last stage wrote.
+//
+// The stage chain.  Behind its resize kernels such a call launches at most
+// three stages, in this order: the warp stage (warp.hip; a warp call), the
+// enhance stage (enhance.hip; an enhance call), the second pass
+// (row_stage.hip: format_rows for the images of a formatted call that no wave
+// kernel takes; pixel_rows for every image of a colour or tone call, and,
+// with identity matrices, of a warp or enhance call with a format alone).
+// One rule places their rows.  The resize kernels write u8 scratch rows A.
+// Every stage reads the rows the stage before it wrote.  The rows alternate
+// A, B, A (A is dead once the second stage has read B).  The last stage
+// writes the caller's destinations.  Rows B, as large as A, exist when at
+// least two stages follow the resize.
 enum class SecondPass : int32_t { None, Format, Color, Tone };
+enum class StageKind : int32_t { Warp, Enhance, Pass };
+enum class Rows : int32_t { A, B, Dst };
 struct PostOps {
   const mxd_out_format* fmt = nullptr;
   const mxd_color* colors = nullptr;
@@ -330,7 +333,9 @@ struct BatchLayout {
   std::vector<ImgPlan> plans;     // by batch index
   std::vector<int32_t> image_of;  // batch index of descriptor k < n: band, then wave, then general images
   // One upload, in ImgDev-sized blocks: the n descriptors, the unit -> image
-  // tables from tables_at, the second pass's entries from fmt_at.
+  // tables from tables_at, the stages' entries from fmt_at (Stage::at each).
+  // fmt_at is where the tables end, with or without stages; the second pass,
+  // whose entries come first, has at == fmt_at.
   std::vector<ImgDev> descs;
   size_t tables_at = 0, fmt_at = 0;
   std::vector<BandGroup> bands;
@@ -338,55 +343,63 @@ struct BatchLayout {
   int32_t general_at = 0;  // first descriptor of the general kernel
   LaunchCfg general{};     // nimgs == 0: no general launch
   std::vector<Launch> launches;  // largest first
-  // The second pass.  The images it reads are resized into u8 scratch rows:
-  // those no wave kernel takes in a formatted call, every image (wave kernels
-  // in their u8 mode included) in a colour or tone call, whose entries stand
-  // in batch order.  Their descriptors' dst and their entries' src are
-  // offsets into a scratch of scratch_bytes (add_scratch).  fmt_count entries
-  // of entry_size bytes (an FmtRowDev, ColorRowDev or ToneRowDev each, all
-  // starting with the FmtRowDev that entry() returns), fmt_blocks workgroups.
-  SecondPass pass = SecondPass::None;
-  size_t entry_size = 0;
+  // What follows the resize: the stage chain (the rule above PostOps), in
+  // launch order.  A stage's entries lie in the upload from block `at`:
+  // `count` entries of `entry_size` bytes, all beginning with the RowHead that
+  // head() returns (resample.h).  Their src, and their dst unless the stage
+  // writes the destinations, are offsets into a scratch of scratch_bytes
+  // until add_scratch() makes them addresses.
+  struct Stage {
+    StageKind kind;
+    Rows reads, writes;
+    size_t at = 0, entry_size = 0;
+    int32_t count = 0;
+    int32_t blocks = 0;      // workgroups of its kernel over the entries
+    int32_t pre_blocks = 0;  // of the kernel in front of it: warp_tab (the table-path images), tone_hist
+  };
+  Stage chain[3];
+  int32_t nstages = 0;
+  Stage* stage(StageKind k) {
+    for (int32_t s = 0; s < nstages; s++)
+      if (chain[s].kind == k) return &chain[s];
+    return nullptr;
+  }
+  const Stage* stage(StageKind k) const { return const_cast<BatchLayout*>(this)->stage(k); }
+  uint8_t* head(const Stage& st, int32_t j) { return reinterpret_cast<uint8_t*>(descs.data() + st.at) + (size_t)j * st.entry_size; }
+  // The scratch: rows A from 0 (the resize kernels' destinations, 256-byte
+  // aligned each), rows B the same rows b_at (a multiple of 256; 0 without B)
+  // further on, the warp stage's index tables (w + h int32 per table-path
+  // image) from warp_tab_at, a tone call's workspace from tone_ws_at (a
+  // multiple of 256): tone_stat_bytes of statistics (one block per image whose
+  // op needs them; zeroed for every call), then one table per image.
+  // warp_tab, tone_ws: their addresses once add_scratch() knows the scratch.
+  // The second pass reads, in a formatted call, the images no wave kernel
+  // takes; in a colour or tone call every image (wave kernels in their u8 mode
+  // included), entries in batch order.  The other two stages have one entry
+  // per image in batch order.
+  SecondPass pass = SecondPass::None;  // the second pass's kernel
   bool matrix = false;  // pixel_rows applies the entries' matrices (a tone call without colours: the identity, skipped)
   std::vector<mxd_image> images;  // the batch with the destinations the resize kernels write
-  size_t scratch_bytes = 0;
-  int32_t fmt_count = 0, fmt_blocks = 0;
-  mxd::FmtRowDev& entry(int32_t j) {
-    return *reinterpret_cast<mxd::FmtRowDev*>(reinterpret_cast<uint8_t*>(descs.data() + fmt_at) + (size_t)j * entry_size);
-  }
-  // Tone call only.  Behind the scratch rows, from tone_ws_at (a multiple of
-  // 256; counted in scratch_bytes), lies the call's workspace: tone_stat_bytes
-  // of statistics (one block per image whose op needs them; zeroed for every
-  // call), then one table per image.  tone_hist_blocks: tone_hist's
-  // workgroups.  tone_ws: the workspace's address once add_scratch() knows
-  // the scratch.
-  size_t tone_ws_at = 0, tone_stat_bytes = 0;
-  int32_t tone_hist_blocks = 0;
-  uint8_t* tone_ws = nullptr;
-  // Warp call only.  After the second pass's entries, from warp_at, one
-  // WarpRowDev per image in batch order (warp_tiles workgroups).  Their src
-  // are the scratch rows A the resize kernels write.  With a second pass
-  // their dst (and the second pass's src) are scratch rows B, the same rows
-  // warp_b_at (a multiple of 256) further on; else the caller's destinations
-  // and warp_b_at == 0.  The index tables of the images that take the table
-  // path (warp_tab_count of them, w + h int32 each) lie from warp_tab_at,
-  // behind B and before the tone workspace; all counted in scratch_bytes.
-  bool warped = false;
-  size_t warp_at = 0, warp_b_at = 0, warp_tab_at = 0;
-  int32_t warp_tiles = 0, warp_tab_count = 0;
+  size_t scratch_bytes = 0, b_at = 0, warp_tab_at = 0, tone_ws_at = 0, tone_stat_bytes = 0;
   uint8_t* warp_tab = nullptr;
-  mxd::WarpRowDev& warp_entry(int32_t i) { return reinterpret_cast<mxd::WarpRowDev*>(descs.data() + warp_at)[i]; }
-  // Enhance call only.  After the warp stage's entries, from enhance_at, one
-  // EnhanceRowDev per image in batch order (enhance_tiles workgroups).
-  // Without a warp their src are rows A and their dst rows B (the second
-  // pass's src); with one their src are B, which the warp stage then always
-  // writes, and their dst rows A (the second pass's src).  With no second pass
-  // their dst are the caller's destinations.  No third scratch.
-  bool enhanced = false;
-  size_t enhance_at = 0;
-  int32_t enhance_tiles = 0;
+  uint8_t* tone_ws = nullptr;
+  // The chain by its members' names (0 / false for a stage the call has not).
+  bool warped() const { return stage(StageKind::Warp) != nullptr; }
+  bool enhanced() const { return stage(StageKind::Enhance) != nullptr; }
+  size_t warp_at() const { return warped() ? stage(StageKind::Warp)->at : 0; }
+  size_t enhance_at() const { return enhanced() ? stage(StageKind::Enhance)->at : 0; }
+  int32_t warp_tiles() const { return warped() ? stage(StageKind::Warp)->blocks : 0; }
+  int32_t warp_tab_count() const { return warped() ? stage(StageKind::Warp)->pre_blocks : 0; }
+  int32_t enhance_tiles() const { return enhanced() ? stage(StageKind::Enhance)->blocks : 0; }
+  const Stage* second() const { return stage(StageKind::Pass); }
+  size_t entry_size() const { return second() ? second()->entry_size : 0; }
+  int32_t fmt_count() const { return second() ? second()->count : 0; }
+  int32_t fmt_blocks() const { return second() ? second()->blocks : 0; }
+  int32_t tone_hist_blocks() const { return second() ? second()->pre_blocks : 0; }
+  mxd::FmtRowDev& entry(int32_t j) { return *reinterpret_cast<mxd::FmtRowDev*>(head(*second(), j)); }
+  mxd::WarpRowDev& warp_entry(int32_t i) { return *reinterpret_cast<mxd::WarpRowDev*>(head(*stage(StageKind::Warp), i)); }
   mxd::EnhanceRowDev& enhance_entry(int32_t i) {
-    return reinterpret_cast<mxd::EnhanceRowDev*>(descs.data() + enhance_at)[i];
+    return *reinterpret_cast<mxd::EnhanceRowDev*>(head(*stage(StageKind::Enhance), i));
   }
   const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
   void add_scratch(uint8_t* base);

@@ -675,11 +675,10 @@ int raw_enqueue_copies(HostCall& c) {
 int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t device, bool dst_device,
               const mxd_jpeg_image* jpeg, PostOps ops) {
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
-  // the second pass writes device destinations only
-  if (!dst_device && ops.warps) return fail(MXD_ERR_UNSUPPORTED, "mxd: warp calls need device destinations");
-  if (!dst_device && ops.enhances) return fail(MXD_ERR_UNSUPPORTED, "mxd: enhance calls need device destinations");
-  if (!dst_device && ops.tones) return fail(MXD_ERR_UNSUPPORTED, "mxd: tone calls need device destinations");
-  if (!dst_device && ops.colors) return fail(MXD_ERR_UNSUPPORTED, "mxd: colour calls need device destinations");
+  // the stages behind the resize write device destinations only
+  const char* const call = ops.warps ? "warp" : ops.enhances ? "enhance" : ops.tones ? "tone" : "colour";
+  if (!dst_device && ops.per_image())
+    return fail(MXD_ERR_UNSUPPORTED, std::string("mxd: ") + call + " calls need device destinations");
   mxd_out_format f32_fmt;
   if (int rc = prepare_post_ops(images, n, &ops, &out_dtype, &f32_fmt)) return rc;
   const mxd_out_format* const fmt = ops.fmt;

@@ -256,130 +256,99 @@ mxd_out_format abi_format(const OutFormat& f, const Job& j) {
   return o;
 }
 
+// The images of one source kind with their per-image values, image for image.
+template <class Img>
+struct Share {
+  std::vector<Img> images;
+  std::vector<mxd_color> colors;
+  std::vector<mxd_tone> tones;
+  std::vector<mxd_warp> warps;
+  std::vector<mxd_enhance> enhances;
+  void add(const Img& im, const mxd_color& c, const mxd_tone& t, const mxd_warp& w, const mxd_enhance& e) {
+    images.push_back(im), colors.push_back(c), tones.push_back(t), warps.push_back(w), enhances.push_back(e);
+  }
+};
+
+// Of a C ABI call and its JPEG counterpart, the one that takes these images.
+template <class P, class J>
+P for_source(const mxd_image*, P plain, J) { return plain; }
+template <class P, class J>
+J for_source(const mxd_jpeg_image*, P, J jpeg) { return jpeg; }
+
+// What some plan of a launch has: the whole launch then goes through that
+// member's calls, plans without one with the identity / MXD_*_NONE (exact).
+struct Members {
+  bool colored = false, toned = false, warped = false, enhanced = false;
+};
+
+// One call for a share: the entry point of the last stage some plan has
+// (enhance, warp, tone, colour, format, plain), with the arrays of the
+// members no plan has null.
+template <class Img>
+int call_abi(const Share<Img>& s, const Members& m, int32_t dtype, const mxd_out_format* of, int device, bool dst_device) {
+  if (s.images.empty()) return MXD_OK;
+  const Img* im = s.images.data();
+  const int32_t n = (int32_t)s.images.size();
+  const mxd_color* c = m.colored ? s.colors.data() : nullptr;
+  const mxd_tone* t = m.toned ? s.tones.data() : nullptr;
+  const mxd_warp* w = m.warped ? s.warps.data() : nullptr;
+  if (m.enhanced)
+    return for_source(im, mxd_resize_crop_to_device_enhance, mxd_jpeg_resize_crop_to_device_enhance)(
+        im, w, s.enhances.data(), t, c, n, dtype, of, device);
+  if (m.warped)
+    return for_source(im, mxd_resize_crop_to_device_warp, mxd_jpeg_resize_crop_to_device_warp)(im, w, t, c, n, dtype, of, device);
+  if (m.toned)
+    return for_source(im, mxd_resize_crop_to_device_tone, mxd_jpeg_resize_crop_to_device_tone)(im, t, c, n, dtype, of, device);
+  if (m.colored)
+    return for_source(im, mxd_resize_crop_to_device_color, mxd_jpeg_resize_crop_to_device_color)(im, c, n, dtype, of, device);
+  if (of) return for_source(im, mxd_resize_crop_to_device_fmt, mxd_jpeg_resize_crop_to_device_fmt)(im, n, of, device);
+  if (dst_device) return for_source(im, mxd_resize_crop_to_device, mxd_jpeg_resize_crop_to_device)(im, n, dtype, device);
+  return for_source(im, mxd_resize_crop_host, mxd_jpeg_resize_crop_host)(im, n, dtype, device);
+}
+
 int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device, const OutFormat* fmt = nullptr) {
   g_run_calls.fetch_add(1);
-  std::vector<mxd_image> plain;
-  std::vector<mxd_jpeg_image> jp;
+  Share<mxd_image> plain;
+  Share<mxd_jpeg_image> jp;
   std::vector<std::shared_ptr<const JpegSource>> keep;  // alive for the call
-  std::vector<mxd_color> pc, jc;  // the colours of `plain` and `jp`, image for image
-  std::vector<mxd_tone> pt, jt;   // and their tones
-  std::vector<mxd_warp> pw, jw;   // and their warps
-  std::vector<mxd_enhance> pe, je;  // and their enhance ops
-  bool colored = false, toned = false, warped = false, enhanced = false;
+  Members m;
   for (size_t i = 0; i < n; i++) {
     const Job& j = jobs[i];
     mxd_color c;
     std::memcpy(c.m, j.plan.color.data(), sizeof c.m);
-    colored = colored || j.plan.colored;
+    m.colored = m.colored || j.plan.colored;
     mxd_tone t{};  // (MXD_TONE_NONE for a plan without a tone op)
     if (j.plan.toned) t.op = j.plan.tone_op, t.arg = j.plan.tone_arg, t.factor = j.plan.tone_factor;
-    toned = toned || j.plan.toned;
+    m.toned = m.toned || j.plan.toned;
     mxd_warp w{};  // (MXD_WARP_NONE for a plan without a warp)
     if (j.plan.warped) {
       w.mode = j.plan.warp_mode;
       std::memcpy(w.fill, j.plan.warp_fill.data(), sizeof w.fill);
       std::memcpy(w.m, j.plan.warp_m.data(), sizeof w.m);
     }
-    warped = warped || j.plan.warped;
+    m.warped = m.warped || j.plan.warped;
     mxd_enhance e{};  // (MXD_ENHANCE_NONE for a plan without an enhance op)
     if (j.plan.enhanced) e.op = j.plan.enhance_op, e.factor = j.plan.enhance_factor;
-    enhanced = enhanced || j.plan.enhanced;
+    m.enhanced = m.enhanced || j.plan.enhanced;
     if (auto src = j.plan.src->jpeg()) {
-      jp.push_back(jpeg_desc(j.plan, *src, j.dst, j.stride));
-      jc.push_back(c);
-      jt.push_back(t);
-      jw.push_back(w);
-      je.push_back(e);
+      jp.add(jpeg_desc(j.plan, *src, j.dst, j.stride), c, t, w, e);
       keep.push_back(std::move(src));
     } else {
-      plain.push_back(plan_desc(j.plan, j.dst, j.stride));
-      pc.push_back(c);
-      pt.push_back(t);
-      pw.push_back(w);
-      pe.push_back(e);
+      plain.add(plan_desc(j.plan, j.dst, j.stride), c, t, w, e);
     }
   }
-  g_run_jpeg.fetch_add((int64_t)jp.size());
-  // Some plan is enhanced: the whole launch goes through the _enhance calls,
-  // plans without an enhance op with MXD_ENHANCE_NONE; warps, tones and
-  // matrices only if some plan has them.  Device destinations only.
-  if (enhanced) {
-    if (!dst_device) throw std::logic_error("mxd: an enhance launch needs device destinations");
-    mxd_out_format of{};
-    if (fmt) of = abi_format(*fmt, jobs[0]);
-    if (!jp.empty())
-      if (int rc = mxd_jpeg_resize_crop_to_device_enhance(jp.data(), warped ? jw.data() : nullptr, je.data(),
-                                                          toned ? jt.data() : nullptr, colored ? jc.data() : nullptr,
-                                                          (int32_t)jp.size(), dtype, fmt ? &of : nullptr, device))
-        return rc;
-    if (plain.empty()) return MXD_OK;
-    return mxd_resize_crop_to_device_enhance(plain.data(), warped ? pw.data() : nullptr, pe.data(),
-                                             toned ? pt.data() : nullptr, colored ? pc.data() : nullptr,
-                                             (int32_t)plain.size(), dtype, fmt ? &of : nullptr, device);
+  g_run_jpeg.fetch_add((int64_t)jp.images.size());
+  // Per-image members and formatted outputs: device destinations only
+  // (mxd_*_to_device_*); a formatted launch for host destinations is none.
+  if (const char* what = m.enhanced ? "an enhance" : m.warped ? "a warp" : m.toned ? "a tone" : m.colored ? "a colour" : nullptr) {
+    if (!dst_device) throw std::logic_error(std::string("mxd: ") + what + " launch needs device destinations");
+  } else if (fmt && (!dst_device || n == 0)) {
+    return MXD_OK;
   }
-  // Some plan is warped: the whole launch goes through the _warp calls, plans
-  // without a warp with MXD_WARP_NONE; tones and matrices only if some plan
-  // has them.  Device destinations only.
-  if (warped) {
-    if (!dst_device) throw std::logic_error("mxd: a warp launch needs device destinations");
-    mxd_out_format of{};
-    if (fmt) of = abi_format(*fmt, jobs[0]);
-    if (!jp.empty())
-      if (int rc = mxd_jpeg_resize_crop_to_device_warp(jp.data(), jw.data(), toned ? jt.data() : nullptr,
-                                                       colored ? jc.data() : nullptr, (int32_t)jp.size(), dtype,
-                                                       fmt ? &of : nullptr, device))
-        return rc;
-    if (plain.empty()) return MXD_OK;
-    return mxd_resize_crop_to_device_warp(plain.data(), pw.data(), toned ? pt.data() : nullptr,
-                                          colored ? pc.data() : nullptr, (int32_t)plain.size(), dtype,
-                                          fmt ? &of : nullptr, device);
-  }
-  // Some plan is toned: the whole launch goes through the _tone calls, plans
-  // without a tone op with MXD_TONE_NONE; no matrices unless some plan is
-  // coloured (then the others get the identity).  Device destinations only.
-  if (toned) {
-    if (!dst_device) throw std::logic_error("mxd: a tone launch needs device destinations");
-    mxd_out_format of{};
-    if (fmt) of = abi_format(*fmt, jobs[0]);
-    if (!jp.empty())
-      if (int rc = mxd_jpeg_resize_crop_to_device_tone(jp.data(), jt.data(), colored ? jc.data() : nullptr,
-                                                       (int32_t)jp.size(), dtype, fmt ? &of : nullptr, device))
-        return rc;
-    if (plain.empty()) return MXD_OK;
-    return mxd_resize_crop_to_device_tone(plain.data(), pt.data(), colored ? pc.data() : nullptr, (int32_t)plain.size(),
-                                          dtype, fmt ? &of : nullptr, device);
-  }
-  // Some plan is coloured: the whole launch goes through the _color calls,
-  // plans without a colour with the identity (exact).  Device destinations only.
-  if (colored) {
-    if (!dst_device) throw std::logic_error("mxd: a colour launch needs device destinations");
-    mxd_out_format of{};
-    if (fmt) of = abi_format(*fmt, jobs[0]);
-    if (!jp.empty())
-      if (int rc = mxd_jpeg_resize_crop_to_device_color(jp.data(), jc.data(), (int32_t)jp.size(), dtype,
-                                                        fmt ? &of : nullptr, device))
-        return rc;
-    if (plain.empty()) return MXD_OK;
-    return mxd_resize_crop_to_device_color(plain.data(), pc.data(), (int32_t)plain.size(), dtype, fmt ? &of : nullptr,
-                                           device);
-  }
-  if (fmt) {
-    // formatted outputs: device destinations only (mxd_*_to_device_fmt)
-    if (!dst_device || n == 0) return MXD_OK;
-    const mxd_out_format of = abi_format(*fmt, jobs[0]);
-    if (!jp.empty())
-      if (int rc = mxd_jpeg_resize_crop_to_device_fmt(jp.data(), (int32_t)jp.size(), &of, device)) return rc;
-    if (plain.empty()) return MXD_OK;
-    return mxd_resize_crop_to_device_fmt(plain.data(), (int32_t)plain.size(), &of, device);
-  }
-  if (!jp.empty()) {
-    const int rc = dst_device ? mxd_jpeg_resize_crop_to_device(jp.data(), (int32_t)jp.size(), dtype, device)
-                              : mxd_jpeg_resize_crop_host(jp.data(), (int32_t)jp.size(), dtype, device);
-    if (rc != MXD_OK) return rc;
-  }
-  if (plain.empty()) return MXD_OK;
-  return dst_device ? mxd_resize_crop_to_device(plain.data(), (int32_t)plain.size(), dtype, device)
-                    : mxd_resize_crop_host(plain.data(), (int32_t)plain.size(), dtype, device);
+  mxd_out_format of{};
+  if (fmt) of = abi_format(*fmt, jobs[0]);
+  if (int rc = call_abi(jp, m, dtype, fmt ? &of : nullptr, device, dst_device)) return rc;
+  return call_abi(plain, m, dtype, fmt ? &of : nullptr, device, dst_device);
 }
 
 // Persistent host workers per device for the slices of split batches: a

@@ -280,6 +280,26 @@ struct EnhanceRowDev {
 };
 static_assert(sizeof(EnhanceRowDev) == 56, "EnhanceRowDev layout");
 int launch_enhance(const EnhanceRowDev* rows, int nimgs, int ntiles, void* stream);
+// What the entries of every stage behind the resize begin with: the rows the
+// stage reads and writes.  The host places them by one rule for all stages
+// (capi_internal.h, the stage chain); the rest of an entry is its stage's own.
+struct RowHead {
+  const uint8_t* src;
+  void* dst;
+  int64_t src_stride, dst_stride;
+  int32_t w, h;
+};
+#define MXD_ROW_HEAD(T, W, H)                                                                                   \
+  static_assert(offsetof(T, src) == offsetof(RowHead, src) && offsetof(T, dst) == offsetof(RowHead, dst) &&     \
+                    offsetof(T, src_stride) == offsetof(RowHead, src_stride) &&                                 \
+                    offsetof(T, dst_stride) == offsetof(RowHead, dst_stride) &&                                 \
+                    offsetof(T, W) == offsetof(RowHead, w) && offsetof(T, H) == offsetof(RowHead, h) &&         \
+                    sizeof(((T*)nullptr)->dst) == sizeof(void*),                                                \
+                #T " begins with a RowHead")
+MXD_ROW_HEAD(FmtRowDev, crop_w, crop_h);
+MXD_ROW_HEAD(WarpRowDev, w, h);
+MXD_ROW_HEAD(EnhanceRowDev, w, h);
+#undef MXD_ROW_HEAD
 // Waves of this configuration the device runs at once (occupancy x CUs), 0 if unknown.
 int wave_capacity(const WaveCfg& cfg, int device);
 // Diagnostics: the occupancy API's blocks per CU, the kernel's VGPRs and LDS

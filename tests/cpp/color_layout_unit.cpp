@@ -65,7 +65,7 @@ int main() {
     mxd_set_kernel_policy(prefer_band ? MXD_POLICY_PREFER_BAND : MXD_POLICY_AUTO);
     BatchLayout L;
     CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{f, colors.data()}, &L) == MXD_OK);
-    CHECK(L.pass == SecondPass::Color && L.matrix && L.entry_size == sizeof(mxd::ColorRowDev) && L.n == n && (int32_t)L.image_of.size() == n);
+    CHECK(L.pass == SecondPass::Color && L.matrix && L.entry_size() == sizeof(mxd::ColorRowDev) && L.n == n && (int32_t)L.image_of.size() == n);
     // the routes are those of a plain u8 call: all three kernel families
     CHECK(!L.plans[0].wave && !L.plans[0].band && !L.plans[2].wave && !L.plans[2].band);
     CHECK(L.general.nimgs == 2);
@@ -93,7 +93,7 @@ int main() {
     }
     CHECK(end_max <= L.scratch_bytes);
     // one entry per image, in batch order, with the image's own matrix and destination
-    CHECK(L.fmt_count == n);
+    CHECK(L.fmt_count() == n);
     CHECK(L.descs.size() >= L.fmt_at + ((size_t)n * sizeof(mxd::ColorRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
     int32_t blocks = 0;
     for (int32_t i = 0; i < n; i++) {
@@ -108,7 +108,7 @@ int main() {
       CHECK(r.blk_begin == blocks);
       blocks += (imgs[i].crop_h + mxd::kPixelRows - 1) / mxd::kPixelRows;
     }
-    CHECK(L.fmt_blocks == blocks);
+    CHECK(L.fmt_blocks() == blocks);
     // scratch offsets become addresses for every descriptor and every entry
     uint8_t* base = reinterpret_cast<uint8_t*>(uintptr_t(1) << 32);
     std::vector<uintptr_t> offs(n);
@@ -131,7 +131,7 @@ int main() {
   // without colours the layout is the plain call's
   BatchLayout P;
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{}, &P) == MXD_OK);
-  CHECK(P.pass == SecondPass::None && P.fmt_count == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
+  CHECK(P.pass == SecondPass::None && P.fmt_count() == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
   std::printf("ok %d\n", g_checks);
   return 0;
 }

@@ -86,7 +86,7 @@ int main() {
     mxd_set_kernel_policy(prefer_band ? MXD_POLICY_PREFER_BAND : MXD_POLICY_AUTO);
     BatchLayout L, Q;
     CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{f, cols, tn, wp, enh.data()}, &L) == MXD_OK);
-    CHECK(L.enhanced && L.warped == (wp != nullptr) && L.n == n);
+    CHECK(L.enhanced() && L.warped() == (wp != nullptr) && L.n == n);
     // what follows the stage: pixel_rows in a tone or colour call's layout (a format alone: identity matrices), or nothing
     CHECK(L.pass == (tn ? SecondPass::Tone : follows ? SecondPass::Color : SecondPass::None));
     // the routes and the resize descriptors are those of the same call without the stages, all of them into scratch rows A
@@ -107,8 +107,8 @@ int main() {
       if (wp) {
         // the warp writes B (always: this stage reads it), this stage reads B and writes A or the destinations
         const mxd::WarpRowDev& w = L.warp_entry(i);
-        CHECK(off_of(w.src) == off && off_of(w.dst) == off + L.warp_b_at && w.dst_stride == w.src_stride);
-        CHECK(off_of(e.src) == off + L.warp_b_at);
+        CHECK(off_of(w.src) == off && off_of(w.dst) == off + L.b_at && w.dst_stride == w.src_stride);
+        CHECK(off_of(e.src) == off + L.b_at);
         if (follows) {
           CHECK(off_of(e.dst) == off && e.dst_stride == e.src_stride);
           CHECK(off_of(L.entry(i).src) == off && L.entry(i).src_stride == e.src_stride);
@@ -117,26 +117,26 @@ int main() {
         // this stage reads A and writes B or the destinations
         CHECK(off_of(e.src) == off);
         if (follows) {
-          CHECK(off_of(e.dst) == off + L.warp_b_at && e.dst_stride == e.src_stride);
-          CHECK(off_of(L.entry(i).src) == off + L.warp_b_at && L.entry(i).src_stride == e.src_stride);
+          CHECK(off_of(e.dst) == off + L.b_at && e.dst_stride == e.src_stride);
+          CHECK(off_of(L.entry(i).src) == off + L.b_at && L.entry(i).src_stride == e.src_stride);
         }
       }
       if (follows) CHECK(L.entry(i).dst == imgs[i].dst && L.entry(i).dst_stride == imgs[i].dst_stride);
       else CHECK(e.dst == imgs[i].dst && e.dst_stride == imgs[i].dst_stride);
     }
-    if (has_b) CHECK(L.warp_b_at % 256 == 0 && L.warp_b_at >= a_end);
-    else CHECK(L.warp_b_at == 0);
-    if (follows) CHECK(L.fmt_count == n);
-    else CHECK(L.fmt_count == 0 && L.fmt_blocks == 0);
+    if (has_b) CHECK(L.b_at % 256 == 0 && L.b_at >= a_end);
+    else CHECK(L.b_at == 0);
+    if (follows) CHECK(L.fmt_count() == n);
+    else CHECK(L.fmt_count() == 0 && L.fmt_blocks() == 0);
     // no third scratch: A, B, then the tone workspace
-    const size_t b_end = has_b ? L.warp_b_at + a_end : a_end;
+    const size_t b_end = has_b ? L.b_at + a_end : a_end;
     if (tn) CHECK(L.tone_ws_at % 256 == 0 && L.tone_ws_at >= b_end && L.tone_ws_at < b_end + 512 && L.scratch_bytes > L.tone_ws_at);
     else CHECK(L.scratch_bytes >= b_end && L.scratch_bytes < b_end + 512);
     // the entries: behind the second pass's and the warp stage's
-    const size_t fmt_end = L.fmt_at + ((size_t)L.fmt_count * L.entry_size + sizeof(ImgDev) - 1) / sizeof(ImgDev);
-    if (wp) CHECK(L.warp_at >= fmt_end && L.enhance_at == L.warp_at + ((size_t)n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
-    else CHECK(L.enhance_at >= fmt_end);
-    CHECK(L.descs.size() == L.enhance_at + ((size_t)n * sizeof(mxd::EnhanceRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+    const size_t fmt_end = L.fmt_at + ((size_t)L.fmt_count() * L.entry_size() + sizeof(ImgDev) - 1) / sizeof(ImgDev);
+    if (wp) CHECK(L.warp_at() >= fmt_end && L.enhance_at() == L.warp_at() + ((size_t)n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+    else CHECK(L.enhance_at() >= fmt_end);
+    CHECK(L.descs.size() == L.enhance_at() + ((size_t)n * sizeof(mxd::EnhanceRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
     int32_t tiles = 0;
     for (int32_t i = 0; i < n; i++) {
       const mxd::EnhanceRowDev& e = L.enhance_entry(i);
@@ -145,7 +145,7 @@ int main() {
       CHECK(e.tile_begin == tiles && e.tiles_x == (e.w + mxd::kEnhTileW - 1) / mxd::kEnhTileW);
       tiles += e.tiles_x * ((e.h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
     }
-    CHECK(L.enhance_tiles == tiles);
+    CHECK(L.enhance_tiles() == tiles);
     // scratch offsets become addresses
     uint8_t* base = reinterpret_cast<uint8_t*>(uintptr_t(1) << 32);
     std::vector<uintptr_t> offs(n);
@@ -155,9 +155,9 @@ int main() {
       const int32_t i = L.image_of[k];
       const mxd::EnhanceRowDev& e = L.enhance_entry(i);
       CHECK(L.descs[k].dst == base + offs[k]);
-      CHECK(e.src == base + offs[k] + (wp ? L.warp_b_at : 0));
+      CHECK(e.src == base + offs[k] + (wp ? L.b_at : 0));
       if (wp) CHECK(L.warp_entry(i).src == base + offs[k] && L.warp_entry(i).dst == e.src);
-      if (follows) CHECK(e.dst == base + offs[k] + (wp ? 0 : L.warp_b_at) && L.entry(i).src == e.dst);
+      if (follows) CHECK(e.dst == base + offs[k] + (wp ? 0 : L.b_at) && L.entry(i).src == e.dst);
       else CHECK(e.dst == imgs[i].dst);
     }
     if (tn) CHECK(L.tone_ws == base + L.tone_ws_at);
@@ -173,9 +173,9 @@ int main() {
   const BatchLayout* all[3] = {&A, &B, &C};
   for (int a = 0; a < 3; a++)
     for (int b = a + 1; b < 3; b++) {
-      CHECK(all[a]->descs.size() == all[b]->descs.size() && all[a]->enhance_at == all[b]->enhance_at);
+      CHECK(all[a]->descs.size() == all[b]->descs.size() && all[a]->enhance_at() == all[b]->enhance_at());
       CHECK(std::memcmp(all[a]->descs.data(), all[b]->descs.data(), A.descs.size() * sizeof(ImgDev)) != 0);
-      CHECK(std::memcmp(all[a]->descs.data(), all[b]->descs.data(), A.enhance_at * sizeof(ImgDev)) == 0);
+      CHECK(std::memcmp(all[a]->descs.data(), all[b]->descs.data(), A.enhance_at() * sizeof(ImgDev)) == 0);
     }
   // what MXD_ENHANCE_NONE does not read does not reach the upload
   enh[1].factor = 77.0f;
@@ -191,14 +191,14 @@ int main() {
   // without enhance ops the layouts are what they were
   BatchLayout W, K, P;
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{&fmt, nullptr, nullptr, warps.data()}, &W) == MXD_OK);
-  CHECK(!W.enhanced && W.enhance_tiles == 0 && W.enhance_at == 0);
-  CHECK(W.descs.size() == W.warp_at + ((size_t)n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+  CHECK(!W.enhanced() && W.enhance_tiles() == 0 && W.enhance_at() == 0);
+  CHECK(W.descs.size() == W.warp_at() + ((size_t)n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
   CHECK(off_of(W.entry(0).src) == off_of(W.warp_entry(0).dst));
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, colors.data()}, &K) == MXD_OK);
-  CHECK(!K.enhanced && !K.warped && K.warp_b_at == 0 &&
+  CHECK(!K.enhanced() && !K.warped() && K.b_at == 0 &&
         K.descs.size() == K.fmt_at + ((size_t)n * sizeof(mxd::ColorRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{}, &P) == MXD_OK);
-  CHECK(!P.enhanced && P.pass == SecondPass::None && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
+  CHECK(!P.enhanced() && P.pass == SecondPass::None && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
   std::printf("ok %d\n", g_checks);
   return 0;
 }

@@ -161,7 +161,7 @@ static void test_layout() {
   BatchLayout F;
   CHECK(build_layout(env, 0, imgs, 3, nullptr, MXD_U8, &fmt, &F) == MXD_OK);
   CHECK(F.plans[0].wave && !F.plans[1].wave && !F.plans[2].wave);
-  CHECK(F.fmt_count == 2 && F.scratch_bytes > 0);
+  CHECK(F.fmt_count() == 2 && F.scratch_bytes > 0);
   // large sources: triangle groups take streaming loads, cubic groups the default policy
   std::vector<mxd_image> many(400, center(1280, 960, 256, 224, false, 0));
   for (size_t i = 200; i < many.size(); i++) many[i].filter = 1;

@@ -418,13 +418,13 @@ static void test_layout_formatted(int32_t policy) {
     for (auto& r : ranges) CHECK(off >= r.first + r.second || off + size <= r.first);
     ranges.push_back({off, size});
     need += size;
-    CHECK(rows < L.fmt_count);
+    CHECK(rows < L.fmt_count());
     const mxd::FmtRowDev& e = L.entry(rows++);
     CHECK(e.src == d.dst && e.src_stride == d.dst_stride && e.dst == imgs[i].dst && e.dst_stride == imgs[i].dst_stride);
     CHECK(e.crop_w == d.crop_w && e.crop_h == d.crop_h && e.channels == 3 && e.blk_begin == blocks);
     blocks += (d.crop_h + mxd::kFmtRows - 1) / mxd::kFmtRows;
   }
-  CHECK(rows == L.fmt_count && blocks == L.fmt_blocks && need == L.scratch_bytes);
+  CHECK(rows == L.fmt_count() && blocks == L.fmt_blocks() && need == L.scratch_bytes);
   for (auto& r : ranges) CHECK(r.first + r.second <= need);
   CHECK(rows >= 1);
   CHECK(L.descs.size() == L.fmt_at + ((size_t)rows * sizeof(mxd::FmtRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));

@@ -75,7 +75,7 @@ int main() {
     mxd_set_kernel_policy(prefer_band ? MXD_POLICY_PREFER_BAND : MXD_POLICY_AUTO);
     BatchLayout L;
     CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{f, cols, tones.data()}, &L) == MXD_OK);
-    CHECK(L.pass == SecondPass::Tone && L.entry_size == sizeof(mxd::ToneRowDev) && L.n == n && (int32_t)L.image_of.size() == n);
+    CHECK(L.pass == SecondPass::Tone && L.entry_size() == sizeof(mxd::ToneRowDev) && L.n == n && (int32_t)L.image_of.size() == n);
     CHECK(L.matrix == (cols != nullptr));
     // the routes are those of a plain u8 call
     CHECK(!L.plans[0].wave && !L.plans[0].band && !L.plans[2].wave && !L.plans[2].band);
@@ -97,7 +97,7 @@ int main() {
     // the workspace: one statistics block per image that needs one, then a table per image
     CHECK(L.tone_stat_bytes == 4 * stat_block);
     CHECK(L.scratch_bytes == L.tone_ws_at + L.tone_stat_bytes + (size_t)n * mxd::kToneLutBytes);
-    CHECK(L.fmt_count == n);
+    CHECK(L.fmt_count() == n);
     CHECK(L.descs.size() >= L.fmt_at + ((size_t)n * sizeof(mxd::ToneRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
     int32_t blocks = 0, hist = 0, nstat = 0;
     for (int32_t i = 0; i < n; i++) {
@@ -121,7 +121,7 @@ int main() {
       CHECK((size_t)r.lut_off + mxd::kToneLutBytes <= L.scratch_bytes - L.tone_ws_at);
       blocks += (imgs[i].crop_h + mxd::kPixelRows - 1) / mxd::kPixelRows;
     }
-    CHECK(L.fmt_blocks == blocks && L.tone_hist_blocks == hist && hist > 0);
+    CHECK(L.fmt_blocks() == blocks && L.tone_hist_blocks() == hist && hist > 0);
     // tone_hist's search (the last image whose hist_begin <= block) finds an image with statistics
     for (int32_t blk = 0; blk < hist; blk++) {
       int32_t found = 0;
@@ -149,7 +149,7 @@ int main() {
     flat[2].op = MXD_TONE_NONE;
     BatchLayout L;
     CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, nullptr, flat.data()}, &L) == MXD_OK);
-    CHECK(L.tone_hist_blocks == 0 && L.tone_stat_bytes == 0 && L.fmt_blocks > 0);
+    CHECK(L.tone_hist_blocks() == 0 && L.tone_stat_bytes == 0 && L.fmt_blocks() > 0);
     for (int32_t i = 0; i < n; i++) CHECK(tone_entry(L, i).stat_off == -1 && tone_entry(L, i).hist_begin == 0);
   }
   // other ops or parameters, other upload: the cached descriptor slot is keyed by them
@@ -171,9 +171,9 @@ int main() {
   // without tones the layouts are the colour call's and the plain call's
   BatchLayout K, P;
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, colors.data()}, &K) == MXD_OK);
-  CHECK(K.pass == SecondPass::Color && K.tone_stat_bytes == 0 && K.tone_ws_at == 0 && K.fmt_count == n);
+  CHECK(K.pass == SecondPass::Color && K.tone_stat_bytes == 0 && K.tone_ws_at == 0 && K.fmt_count() == n);
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{}, &P) == MXD_OK);
-  CHECK(P.pass == SecondPass::None && P.fmt_count == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
+  CHECK(P.pass == SecondPass::None && P.fmt_count() == 0 && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
   std::printf("ok %d\n", g_checks);
   return 0;
 }

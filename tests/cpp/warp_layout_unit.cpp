@@ -84,7 +84,7 @@ int main() {
     mxd_set_kernel_policy(prefer_band ? MXD_POLICY_PREFER_BAND : MXD_POLICY_AUTO);
     BatchLayout L, Q;
     CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{f, cols, tn, warps.data()}, &L) == MXD_OK);
-    CHECK(L.warped && L.n == n);
+    CHECK(L.warped() && L.n == n);
     // what follows the warp: pixel_rows in a tone or colour call's layout (a format alone: identity matrices), or nothing
     CHECK(L.pass == (tn ? SecondPass::Tone : follows ? SecondPass::Color : SecondPass::None));
     // the routes and the resize descriptors are those of the same call without warps, all of them into scratch rows A
@@ -100,24 +100,24 @@ int main() {
       const mxd::WarpRowDev& e = L.warp_entry(i);
       CHECK(reinterpret_cast<uintptr_t>(e.src) == off && e.src_stride == L.descs[k].dst_stride);
       if (follows) {
-        // scratch rows B: the same rows, warp_b_at further on, read by the second pass
-        CHECK(reinterpret_cast<uintptr_t>(e.dst) == off + L.warp_b_at && e.dst_stride == e.src_stride);
-        CHECK(reinterpret_cast<uintptr_t>(L.entry(i).src) == off + L.warp_b_at && L.entry(i).src_stride == e.src_stride);
+        // scratch rows B: the same rows, b_at further on, read by the second pass
+        CHECK(reinterpret_cast<uintptr_t>(e.dst) == off + L.b_at && e.dst_stride == e.src_stride);
+        CHECK(reinterpret_cast<uintptr_t>(L.entry(i).src) == off + L.b_at && L.entry(i).src_stride == e.src_stride);
         CHECK(L.entry(i).dst == imgs[i].dst && L.entry(i).dst_stride == imgs[i].dst_stride);
       } else {
         CHECK(e.dst == imgs[i].dst && e.dst_stride == imgs[i].dst_stride);  // no B: the caller's destination
       }
     }
-    if (follows) CHECK(L.warp_b_at % 256 == 0 && L.warp_b_at >= a_end && L.fmt_count == n);
-    else CHECK(L.warp_b_at == 0 && L.fmt_count == 0 && L.fmt_blocks == 0);
-    const size_t b_end = follows ? L.warp_b_at + a_end : a_end;
+    if (follows) CHECK(L.b_at % 256 == 0 && L.b_at >= a_end && L.fmt_count() == n);
+    else CHECK(L.b_at == 0 && L.fmt_count() == 0 && L.fmt_blocks() == 0);
+    const size_t b_end = follows ? L.b_at + a_end : a_end;
     // the tables: behind B, before the tone workspace, one w + h int32 block per table image
-    CHECK(L.warp_tab_count == 2 && L.warp_tab_at % 256 == 0 && L.warp_tab_at >= b_end);
+    CHECK(L.warp_tab_count() == 2 && L.warp_tab_at % 256 == 0 && L.warp_tab_at >= b_end);
     const size_t tab_end = L.warp_tab_at + (40 + 40) * 4 * 2;
     if (tn) CHECK(L.tone_ws_at % 256 == 0 && L.tone_ws_at >= tab_end && L.scratch_bytes > L.tone_ws_at);
     else CHECK(L.scratch_bytes == tab_end);
-    CHECK(L.warp_at >= L.fmt_at + ((size_t)L.fmt_count * L.entry_size + sizeof(ImgDev) - 1) / sizeof(ImgDev));
-    CHECK(L.descs.size() == L.warp_at + ((size_t)n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+    CHECK(L.warp_at() >= L.fmt_at + ((size_t)L.fmt_count() * L.entry_size() + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+    CHECK(L.descs.size() == L.warp_at() + ((size_t)n * sizeof(mxd::WarpRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
     int32_t tiles = 0, tabs = 0;
     for (int32_t i = 0; i < n; i++) {
       const mxd::WarpRowDev& e = L.warp_entry(i);
@@ -133,7 +133,7 @@ int main() {
         CHECK(e.tab_index == -1);
       }
     }
-    CHECK(L.warp_tiles == tiles && tabs == 2);
+    CHECK(L.warp_tiles() == tiles && tabs == 2);
     // scratch offsets become addresses
     uint8_t* base = reinterpret_cast<uint8_t*>(uintptr_t(1) << 32);
     std::vector<uintptr_t> offs(n);
@@ -142,7 +142,7 @@ int main() {
     for (int32_t k = 0; k < n; k++) {
       const int32_t i = L.image_of[k];
       CHECK(L.descs[k].dst == base + offs[k] && L.warp_entry(i).src == base + offs[k]);
-      if (follows) CHECK(L.warp_entry(i).dst == base + offs[k] + L.warp_b_at && L.entry(i).src == L.warp_entry(i).dst);
+      if (follows) CHECK(L.warp_entry(i).dst == base + offs[k] + L.b_at && L.entry(i).src == L.warp_entry(i).dst);
       else CHECK(L.warp_entry(i).dst == imgs[i].dst);
     }
     CHECK(L.warp_tab == base + L.warp_tab_at);
@@ -155,7 +155,7 @@ int main() {
     w2[2].mode = MXD_WARP_BILINEAR, w2[5].m[1] = 0.25;
     BatchLayout L;
     CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, nullptr, nullptr, w2.data()}, &L) == MXD_OK);
-    CHECK(L.warp_tab_count == 0 && L.warp_entry(5).path == mxd::kWarpFixed);
+    CHECK(L.warp_tab_count() == 0 && L.warp_entry(5).path == mxd::kWarpFixed);
     size_t a_end = 0;
     for (int32_t k = 0; k < n; k++)
       a_end = std::max<size_t>(a_end, reinterpret_cast<uintptr_t>(L.descs[k].dst) +
@@ -174,9 +174,9 @@ int main() {
   const BatchLayout* all[4] = {&A, &B, &C, &D};
   for (int a = 0; a < 4; a++)
     for (int b = a + 1; b < 4; b++) {
-      CHECK(all[a]->descs.size() == all[b]->descs.size() && all[a]->warp_at == all[b]->warp_at);
+      CHECK(all[a]->descs.size() == all[b]->descs.size() && all[a]->warp_at() == all[b]->warp_at());
       CHECK(std::memcmp(all[a]->descs.data(), all[b]->descs.data(), A.descs.size() * sizeof(ImgDev)) != 0);
-      CHECK(std::memcmp(all[a]->descs.data(), all[b]->descs.data(), A.warp_at * sizeof(ImgDev)) == 0);
+      CHECK(std::memcmp(all[a]->descs.data(), all[b]->descs.data(), A.warp_at() * sizeof(ImgDev)) == 0);
     }
   // what MXD_WARP_NONE does not read does not reach the upload
   warps[1].m[0] = 77.0, warps[1].fill[0] = 1;
@@ -186,9 +186,9 @@ int main() {
   // without warps the layouts are what they were
   BatchLayout K, P;
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{nullptr, colors.data()}, &K) == MXD_OK);
-  CHECK(!K.warped && K.warp_b_at == 0 && K.warp_tiles == 0 && K.descs.size() == K.fmt_at + ((size_t)n * sizeof(mxd::ColorRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+  CHECK(!K.warped() && K.b_at == 0 && K.warp_tiles() == 0 && K.descs.size() == K.fmt_at + ((size_t)n * sizeof(mxd::ColorRowDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
   CHECK(build_layout(env, 0, imgs.data(), n, nullptr, MXD_U8, PostOps{}, &P) == MXD_OK);
-  CHECK(!P.warped && P.pass == SecondPass::None && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
+  CHECK(!P.warped() && P.pass == SecondPass::None && P.scratch_bytes == 0 && P.descs.size() == P.fmt_at);
   std::printf("ok %d\n", g_checks);
   return 0;
 }

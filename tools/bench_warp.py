@@ -143,12 +143,15 @@ def main():
     ap.add_argument("--workloads", default="c2,c4")
     ap.add_argument("--variants", default="")
     ap.add_argument("--out", default="")
+    ap.add_argument("--lib", default="", help="another build of libmxd_amd.so to time (a compile-time variant)")
     args = ap.parse_args()
     import torch  # torch first: its HIP runtime is the one the libraries bind
 
     torch.zeros(1, device="cuda:0")
     from mlx_data_amd import capi
 
+    if args.lib:
+        capi.LIB_PATH = os.path.abspath(args.lib)
     capi.check(capi.lib().mxd_set_device(0))
     out = open(args.out, "a") if args.out else None
 
@@ -161,6 +164,7 @@ def main():
 
     name, arch, cus = capi.device_properties(0)
     emit({"device": name, "arch": arch, "cus": cus, "rounds": args.rounds, "torch": torch.__version__,
+          "lib": os.path.basename(args.lib) if args.lib else "product",
           "method": "bench.launch_windows: device events, windows >= 100 launches and >= 20 ms, 3 per round"})
     only = set(args.variants.split(",")) if args.variants else set()
     for wl in args.workloads.split(","):
