@@ -71,13 +71,18 @@ extern "C" {
  * 7, added without a new number (test for MXD_HAS_ENHANCE / the symbols): the
  * per-image enhance operations -- mxd_enhance_op, mxd_enhance,
  * mxd_enhance_validate, mxd_enhance_apply_u8, mxd_resize_crop_batch_enhance,
- * mxd_resize_crop_to_device_enhance, mxd_jpeg_resize_crop_to_device_enhance. */
+ * mxd_resize_crop_to_device_enhance, mxd_jpeg_resize_crop_to_device_enhance.
+ * 7, added without a new number (test for MXD_HAS_MIX / the symbols): MixUp
+ * and CutMix across the images of a call -- mxd_mix_op, mxd_mix,
+ * mxd_mix_validate, mxd_mix_apply_u8, mxd_resize_crop_batch_mix,
+ * mxd_resize_crop_to_device_mix, mxd_jpeg_resize_crop_to_device_mix. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
 #define MXD_HAS_TONE 1
 #define MXD_HAS_WARP 1
 #define MXD_HAS_ENHANCE 1
+#define MXD_HAS_MIX 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -788,6 +793,82 @@ int mxd_resize_crop_to_device_enhance(const mxd_image* images, const mxd_warp* w
 int mxd_jpeg_resize_crop_to_device_enhance(const mxd_jpeg_image* images, const mxd_warp* warps,
                                            const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
                                            int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
+
+/* ---- MixUp and CutMix across the images of a call (ABI 7 additions; feature
+ * test: MXD_HAS_MIX)
+ *
+ * A mix acts on the u8 RGB results of two images of the same call -- each
+ * after its geometry, warp, enhance, tone and colour -- and before the output
+ * form: the stage order of a call is geometry, warp, enhance, tone, colour,
+ * mix, output form.  It is timm's FastCollateMixup, which mixes the uint8
+ * images before they are normalised.  For image i with partner p, own byte q
+ * and the partner's byte r at the same (x, y, c):
+ *
+ *   NONE    q' = q
+ *   MIXUP   x = ((float)q * w_self) + ((float)r * w_other) in float32, each
+ *           operation rounded and none fused; q' = (uint8) min(rint(x), 255),
+ *           rint rounding half to even -- not the +0.5 truncation of the
+ *           resize.  This is NumPy's
+ *             a.astype(float32) * lam + b.astype(float32) * (1 - lam); rint
+ *           for w_self = (float)lam, w_other = (float)(1.0 - lam) with the
+ *           subtraction in double, which is how a caller passes a lam.  (The
+ *           min is never reached by such a pair: it only defines the result
+ *           of weights that do not sum to one.)
+ *   CUTMIX  q' = r for x0 <= x < x1 and y0 <= y < y1, else q.  The box is in
+ *           the crop window's coordinates: in the result, after the mirror
+ *           and the warp.
+ *
+ * r is the partner's own unmixed result: every image reads what the stage
+ * before the mix wrote and none reads a mixed byte, as timm mixes from the
+ * unmixed batch.  partner == i is allowed and gets no special case. */
+enum mxd_mix_op { MXD_MIX_NONE = 0, MXD_MIX_MIXUP = 1, MXD_MIX_CUTMIX = 2 };
+
+typedef struct mxd_mix {
+  int32_t op;             /* mxd_mix_op; NONE: the other fields (but reserved) are not read */
+  int32_t partner;        /* index into the same call's images */
+  float w_self, w_other;  /* MIXUP; finite, 0..1 each */
+  int32_t x0, y0, x1, y1; /* CUTMIX; 0 <= x0 <= x1 <= crop_w, 0 <= y0 <= y1 <= crop_h */
+  int32_t reserved[2];    /* must be 0 */
+} mxd_mix;
+
+/* Host only: the CPU statement of the arithmetic above on two w x h packed RGB
+ * images (rows own_stride / partner_stride bytes apart) into out (rows
+ * out_stride bytes apart; it may be `own` itself).  mix->partner is not read.
+ * MXD_ERR_INVALID for a bad mix (as the calls below, the box against w x h). */
+int mxd_mix_apply_u8(const uint8_t* own, int64_t own_stride, const uint8_t* partner, int64_t partner_stride,
+                     int32_t w, int32_t h, const mxd_mix* mix, uint8_t* out, int64_t out_stride);
+/* Host only: the checks the calls below make of mixes[0..n) against
+ * images[0..n) (MXD_OK, or MXD_ERR_INVALID with their message).  images may be
+ * NULL: the entries alone (no crop sizes: partners' sizes and the boxes' upper
+ * bounds are not checked). */
+int mxd_mix_validate(const mxd_image* images, const mxd_mix* mixes, int32_t n);
+
+/* The _enhance calls with mixes[i] applied to images[i]'s result last before
+ * the output form.  warps, enhances, tones, colors and fmt may each be NULL;
+ * mixes may not.  Device destinations only; every output form of the _color
+ * calls.  MXD_ERR_INVALID (the message names the image and the field) for a
+ * null mixes, an unknown op, a partner outside [0, n), a partner whose crop_w /
+ * crop_h differ, channels != 3, a bad weight or box, or a non-zero reserved;
+ * everything is validated before any launch.  Every image is resized as a u8
+ * image into a scratch; the stages of the _enhance calls follow in their u8
+ * forms, and one last launch on the same stream (mix_rows) reads two images'
+ * rows per output row and writes the destinations in the call's output form.
+ * The host-source calls stage the whole call as one chunk (a partner must be
+ * on the device with its image): every source of the call is in page-locked
+ * host memory and in device memory at once, beside the u8 scratch rows of the
+ * whole call, so MXD_ERR_UNSUPPORTED past 65535 images or 1 GiB of staged
+ * sources (a JPEG that is entropy-decoded on the device counts an eighth of
+ * its coefficient bytes). */
+int mxd_resize_crop_batch_mix(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                              const mxd_tone* tones, const mxd_color* colors, const mxd_mix* mixes, int32_t n,
+                              int32_t out_dtype, const mxd_out_format* fmt, int32_t device, void* stream);
+int mxd_resize_crop_to_device_mix(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                  const mxd_tone* tones, const mxd_color* colors, const mxd_mix* mixes, int32_t n,
+                                  int32_t out_dtype, const mxd_out_format* fmt, int32_t device);
+int mxd_jpeg_resize_crop_to_device_mix(const mxd_jpeg_image* images, const mxd_warp* warps,
+                                       const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
+                                       const mxd_mix* mixes, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                                       int32_t device);
 
 /* Diagnostics: where a host-side pipeline's time goes, summed over every
  * thread since the last reset (reset != 0 zeroes them after reading).

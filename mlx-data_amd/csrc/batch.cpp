@@ -406,10 +406,16 @@ int launch_all(const BatchLayout& L, const ImgDev* dev, Workspace* ws, const mxd
 }
 
 // One stage of the chain over its entries in the uploaded copy.
-int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDev* dev, const mxd::OutFmtDev& ofd,
+int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDev* dev, const mxd::OutFmtDev& form,
                  void* stream) {
   if (st.count == 0) return MXD_OK;  // (a formatted call whose every image a wave kernel took)
   const void* entries = dev + st.at;
+  // The output form is the last stage's: a second pass in front of the mix
+  // stage writes u8 scratch rows (pixel_rows without a table).
+  const mxd::OutFmtDev ofd = st.writes == Rows::Dst ? form : mxd::OutFmtDev{};
+  // (only a mix call has a second pass that is not the last stage: anywhere else it would drop its format)
+  if (st.kind == StageKind::Pass && st.writes != Rows::Dst && !L.mixed())
+    return fail(MXD_ERR_DEVICE, "mxd: a second pass that does not write the destinations outside a mix call");
   const char* what = "format_rows launch failed: ";
   int rc = 0;
   if (st.kind == StageKind::Warp) {
@@ -418,6 +424,9 @@ int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDe
   } else if (st.kind == StageKind::Enhance) {
     what = "enhance launch failed: ";
     rc = mxd::launch_enhance(static_cast<const mxd::EnhanceRowDev*>(entries), st.count, st.blocks, stream);
+  } else if (st.kind == StageKind::Mix) {
+    what = "mix launch failed: ";
+    rc = mxd::launch_mix(static_cast<const mxd::MixRowDev*>(entries), st.count, st.blocks, ofd, stream);
   } else if (L.pass == SecondPass::Tone) {
     // this call's statistics start from zero, whatever the stream's last call left
     if (L.tone_stat_bytes > 0 &&
@@ -473,6 +482,8 @@ int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* 
     if (int rc = tone_validate(images, ops->tones, n)) return rc;
   if (ops->colors)
     if (int rc = color_validate(images, ops->colors, n)) return rc;
+  if (ops->mixes)
+    if (int rc = mix_validate(images, ops->mixes, n)) return rc;
   if (!ops->fmt) {
     if (*out_dtype != MXD_U8 && *out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
     if (*out_dtype == MXD_F32_DIV255) {

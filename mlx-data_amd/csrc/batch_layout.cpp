@@ -345,12 +345,14 @@ void derive_chain(const PostOps& ops, BatchLayout& L) {
   if (ops.warps) L.chain[L.nstages++].kind = StageKind::Warp;
   if (ops.enhances) L.chain[L.nstages++].kind = StageKind::Enhance;
   if (L.pass != SecondPass::None) L.chain[L.nstages++].kind = StageKind::Pass;
+  if (ops.mixes) L.chain[L.nstages++].kind = StageKind::Mix;
   for (int32_t s = 0; s < L.nstages; s++) {
     BatchLayout::Stage& st = L.chain[s];
     st.reads = s % 2 ? Rows::B : Rows::A;
     st.writes = s == L.nstages - 1 ? Rows::Dst : s % 2 ? Rows::A : Rows::B;
     st.entry_size = st.kind == StageKind::Warp       ? sizeof(mxd::WarpRowDev)
                     : st.kind == StageKind::Enhance  ? sizeof(mxd::EnhanceRowDev)
+                    : st.kind == StageKind::Mix      ? sizeof(mxd::MixRowDev)
                     : L.pass == SecondPass::Tone     ? sizeof(mxd::ToneRowDev)
                     : L.pass == SecondPass::Color    ? sizeof(mxd::ColorRowDev)
                                                      : sizeof(mxd::FmtRowDev);
@@ -425,6 +427,29 @@ void fill_enhances(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
   }
 }
 
+// The mix stage's own fields: partners, ops, weights and boxes are part of the
+// upload's bytes, so a cached slot is reused only for equal mixes.  The
+// partner's rows are those the partner's own entry reads (an offset into the
+// scratch until add_scratch).
+void fill_mixes(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  for (int32_t i = 0; i < b.n; i++) {
+    const mxd_image& im = L.images[i];
+    const mxd_mix& mx = ops.mixes[i];
+    mxd::MixRowDev& e = L.mix_entry(i);
+    e.blk_begin = st.blocks;
+    st.blocks += (im.crop_h + mxd::kMixRows - 1) / mxd::kMixRows;
+    e.op = mx.op;
+    // (MXD_MIX_NONE reads nothing else: zeros, so equal calls make equal bytes)
+    if (mx.op == MXD_MIX_NONE) continue;
+    const mxd::MixRowDev& p = L.mix_entry(mx.partner);
+    e.psrc = p.src;
+    e.psrc_stride = p.src_stride;
+    if (mx.op == MXD_MIX_MIXUP) e.w_self = mx.w_self, e.w_other = mx.w_other;
+    if (mx.op == MXD_MIX_CUTMIX) e.x0 = mx.x0, e.y0 = mx.y0, e.x1 = mx.x1, e.y1 = mx.y1;
+  }
+}
+
 // After every descriptor, in ImgDev-sized blocks: the unit -> image tables of
 // the band launches whose images differ in unit count (int32 each), then the
 // stages' entries (append_stages).
@@ -485,7 +510,8 @@ void fill_second_pass(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
 }
 
 // The chain's scratch behind rows A, then its entries behind the tables: the
-// second pass's first, then the warp stage's, then the enhance stage's.
+// second pass's first, then the warp stage's, the enhance stage's, the mix
+// stage's.
 void append_stages(Batch& b, const mxd_image* callers, const PostOps& ops) {
   BatchLayout& L = b.L;
   if (L.nstages >= 2) {
@@ -498,13 +524,14 @@ void append_stages(Batch& b, const mxd_image* callers, const PostOps& ops) {
     for (int32_t i = 0; i < b.n; i++) tab_bytes += warp_tabled(ops.warps[i]) ? warp_tab_size(L.images[i]) : 0;
     if (tab_bytes > 0) L.scratch_bytes = L.warp_tab_at + tab_bytes;
   }
-  for (StageKind kind : {StageKind::Pass, StageKind::Warp, StageKind::Enhance}) {
+  for (StageKind kind : {StageKind::Pass, StageKind::Warp, StageKind::Enhance, StageKind::Mix}) {
     BatchLayout::Stage* st = L.stage(kind);
     if (!st) continue;
     append_stage(b, callers, *st);
     if (kind == StageKind::Pass) fill_second_pass(b, *st, ops);
     if (kind == StageKind::Warp) fill_warps(b, *st, ops);
     if (kind == StageKind::Enhance) fill_enhances(b, *st, ops);
+    if (kind == StageKind::Mix) fill_mixes(b, *st, ops);
   }
 }
 
@@ -525,6 +552,9 @@ void BatchLayout::add_scratch(uint8_t* base) {
       h.src = base + reinterpret_cast<uintptr_t>(h.src);
       if (chain[s].writes != Rows::Dst) h.dst = base + reinterpret_cast<uintptr_t>(h.dst);
       std::memcpy(head(chain[s], j), &h, sizeof h);
+      // the partner's rows, an offset like src (a NONE entry has none)
+      if (chain[s].kind == StageKind::Mix && mix_entry(j).op != MXD_MIX_NONE)
+        mix_entry(j).psrc = base + reinterpret_cast<uintptr_t>(mix_entry(j).psrc);
     }
   if (pass == SecondPass::Tone) tone_ws = base + tone_ws_at;
   if (warped()) warp_tab = base + warp_tab_at;

@@ -161,7 +161,7 @@ int run_pixmap(const mxd_pixmap* images, int32_t n, int32_t op, int32_t device, 
 
 using namespace mxd::capi;
 
-// The head of the _color, _tone, _warp and _enhance entry points: the format
+// The head of the _color, _tone, _warp, _enhance and _mix entry points: the format
 // when there is one, the call's own array (`required`, named `what`) present,
 // every other member optional; an empty call keeps the format alone.
 static int post_ops(PostOps given, const void* required, const char* what, int32_t n, PostOps* ops) {
@@ -289,6 +289,14 @@ int mxd_resize_crop_batch_enhance(const mxd_image* images, const mxd_warp* warps
                                   const mxd_out_format* fmt, int32_t device, void* stream) {
   PostOps ops;
   if (int rc = post_ops({fmt, colors, tones, warps, enhances}, enhances, "enhances", n, &ops)) return rc;
+  return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
+}
+
+int mxd_resize_crop_batch_mix(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                              const mxd_tone* tones, const mxd_color* colors, const mxd_mix* mixes, int32_t n,
+                              int32_t out_dtype, const mxd_out_format* fmt, int32_t device, void* stream) {
+  PostOps ops;
+  if (int rc = post_ops({fmt, colors, tones, warps, enhances, mixes}, mixes, "mixes", n, &ops)) return rc;
   return run_batch(images, n, out_dtype, device, stream, nullptr, ops);
 }
 
@@ -512,6 +520,14 @@ int mxd_resize_crop_to_device_enhance(const mxd_image* images, const mxd_warp* w
   return host_path(images, n, out_dtype, device, true, nullptr, ops);
 }
 
+int mxd_resize_crop_to_device_mix(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                  const mxd_tone* tones, const mxd_color* colors, const mxd_mix* mixes, int32_t n,
+                                  int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
+  PostOps ops;
+  if (int rc = post_ops({fmt, colors, tones, warps, enhances, mixes}, mixes, "mixes", n, &ops)) return rc;
+  return host_path(images, n, out_dtype, device, true, nullptr, ops);
+}
+
 int mxd_resize_crop_to_device_fmt(const mxd_image* images, int32_t n, const mxd_out_format* fmt, int32_t device) {
   if (int rc = fmt_validate(fmt, 0)) return rc;
   return host_path(images, n, MXD_U8, device, true, nullptr, PostOps{fmt});
@@ -635,6 +651,15 @@ int mxd_jpeg_resize_crop_to_device_enhance(const mxd_jpeg_image* images, const m
                                            int32_t n, int32_t out_dtype, const mxd_out_format* fmt, int32_t device) {
   PostOps ops;
   if (int rc = post_ops({fmt, colors, tones, warps, enhances}, enhances, "enhances", n, &ops)) return rc;
+  return jpeg_path(images, n, out_dtype, device, true, ops);
+}
+
+int mxd_jpeg_resize_crop_to_device_mix(const mxd_jpeg_image* images, const mxd_warp* warps,
+                                       const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
+                                       const mxd_mix* mixes, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                                       int32_t device) {
+  PostOps ops;
+  if (int rc = post_ops({fmt, colors, tones, warps, enhances, mixes}, mixes, "mixes", n, &ops)) return rc;
   return jpeg_path(images, n, out_dtype, device, true, ops);
 }
 

@@ -268,21 +268,27 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
 // to images[i]; colors may be null then (no matrix).  warps: a warp call,
 // warps[i] belongs to images[i]; every other member may be null then.
 // enhances: an enhance call, enhances[i] belongs to images[i]; every other
-// member may be null then.
+// member may be null then.  mixes: a mix call, mixes[i] belongs to images[i] and
+// names its partner among the call's images; every other member may be null
+// then.
 //
 // The stage chain.  Behind its resize kernels such a call launches at most
-// three stages, in this order: the warp stage (warp.hip; a warp call), the
+// four stages, in this order: the warp stage (warp.hip; a warp call), the
 // enhance stage (enhance.hip; an enhance call), the second pass
 // (row_stage.hip: format_rows for the images of a formatted call that no wave
 // kernel takes; pixel_rows for every image of a colour or tone call, and,
-// with identity matrices, of a warp or enhance call with a format alone).
+// with identity matrices, of a warp or enhance call with a format alone), the
+// mix stage (mix.hip; a mix call).  The mix stage is always the last and
+// writes the output form itself: in a mix call the resize kernels run in
+// their u8 mode, a second pass exists only with tones or colours and is
+// pixel_rows in its u8 form, and a format alone makes no second pass.
 // One rule places their rows.  The resize kernels write u8 scratch rows A.
 // Every stage reads the rows the stage before it wrote.  The rows alternate
-// A, B, A (A is dead once the second stage has read B).  The last stage
+// A, B, A, B (A is dead once the second stage has read B).  The last stage
 // writes the caller's destinations.  Rows B, as large as A, exist when at
 // least two stages follow the resize.
 enum class SecondPass : int32_t { None, Format, Color, Tone };
-enum class StageKind : int32_t { Warp, Enhance, Pass };
+enum class StageKind : int32_t { Warp, Enhance, Pass, Mix };
 enum class Rows : int32_t { A, B, Dst };
 struct PostOps {
   const mxd_out_format* fmt = nullptr;
@@ -290,18 +296,20 @@ struct PostOps {
   const mxd_tone* tones = nullptr;
   const mxd_warp* warps = nullptr;
   const mxd_enhance* enhances = nullptr;
+  const mxd_mix* mixes = nullptr;
   // (a format alone, or nullptr, converts: a formatted / plain call)
   PostOps(const mxd_out_format* f = nullptr, const mxd_color* c = nullptr, const mxd_tone* t = nullptr,
-          const mxd_warp* w = nullptr, const mxd_enhance* e = nullptr)
-      : fmt(f), colors(c), tones(t), warps(w), enhances(e) {}
-  bool any() const { return fmt || colors || tones || warps || enhances; }
-  bool per_image() const { return colors || tones || warps || enhances; }  // a colour, tone, warp or enhance call
+          const mxd_warp* w = nullptr, const mxd_enhance* e = nullptr, const mxd_mix* m = nullptr)
+      : fmt(f), colors(c), tones(t), warps(w), enhances(e), mixes(m) {}
+  bool any() const { return fmt || colors || tones || warps || enhances || mixes; }
+  bool per_image() const { return colors || tones || warps || enhances || mixes; }  // a colour, tone, warp, enhance or mix call
   SecondPass pass() const {
-    // (a warp or enhance call with a format alone: pixel_rows with the identity, which is exact)
-    return tones                                  ? SecondPass::Tone
-           : colors || ((warps || enhances) && fmt) ? SecondPass::Color
-           : fmt                                  ? SecondPass::Format
-                                                  : SecondPass::None;
+    // (a warp or enhance call with a format alone: pixel_rows with the identity, which is exact;
+    // a mix call: the mix stage writes the format, so tones and colours alone make a second pass)
+    return tones                                            ? SecondPass::Tone
+           : colors || ((warps || enhances) && fmt && !mixes) ? SecondPass::Color
+           : fmt && !mixes                                  ? SecondPass::Format
+                                                            : SecondPass::None;
   }
   // The resize kernels write the format themselves (wave kernels in their
   // formatted mode).  A colour or tone call's run in their u8 mode into
@@ -310,7 +318,8 @@ struct PostOps {
   // The call's share for the images from `first` on (a host-path chunk).
   PostOps at(int32_t first) const {
     return PostOps{fmt, colors ? colors + first : nullptr, tones ? tones + first : nullptr,
-                   warps ? warps + first : nullptr, enhances ? enhances + first : nullptr};
+                   warps ? warps + first : nullptr, enhances ? enhances + first : nullptr,
+                   mixes ? mixes + first : nullptr};  // (a mix call is one chunk: partners index from `first` = 0)
   }
 };
 
@@ -357,7 +366,7 @@ struct BatchLayout {
     int32_t blocks = 0;      // workgroups of its kernel over the entries
     int32_t pre_blocks = 0;  // of the kernel in front of it: warp_tab (the table-path images), tone_hist
   };
-  Stage chain[3];
+  Stage chain[4];
   int32_t nstages = 0;
   Stage* stage(StageKind k) {
     for (int32_t s = 0; s < nstages; s++)
@@ -375,7 +384,7 @@ struct BatchLayout {
   // warp_tab, tone_ws: their addresses once add_scratch() knows the scratch.
   // The second pass reads, in a formatted call, the images no wave kernel
   // takes; in a colour or tone call every image (wave kernels in their u8 mode
-  // included), entries in batch order.  The other two stages have one entry
+  // included), entries in batch order.  The other stages have one entry
   // per image in batch order.
   SecondPass pass = SecondPass::None;  // the second pass's kernel
   bool matrix = false;  // pixel_rows applies the entries' matrices (a tone call without colours: the identity, skipped)
@@ -391,6 +400,9 @@ struct BatchLayout {
   int32_t warp_tiles() const { return warped() ? stage(StageKind::Warp)->blocks : 0; }
   int32_t warp_tab_count() const { return warped() ? stage(StageKind::Warp)->pre_blocks : 0; }
   int32_t enhance_tiles() const { return enhanced() ? stage(StageKind::Enhance)->blocks : 0; }
+  bool mixed() const { return stage(StageKind::Mix) != nullptr; }
+  size_t mix_at() const { return mixed() ? stage(StageKind::Mix)->at : 0; }
+  int32_t mix_blocks() const { return mixed() ? stage(StageKind::Mix)->blocks : 0; }
   const Stage* second() const { return stage(StageKind::Pass); }
   size_t entry_size() const { return second() ? second()->entry_size : 0; }
   int32_t fmt_count() const { return second() ? second()->count : 0; }
@@ -401,6 +413,7 @@ struct BatchLayout {
   mxd::EnhanceRowDev& enhance_entry(int32_t i) {
     return *reinterpret_cast<mxd::EnhanceRowDev*>(head(*stage(StageKind::Enhance), i));
   }
+  mxd::MixRowDev& mix_entry(int32_t i) { return *reinterpret_cast<mxd::MixRowDev*>(head(*stage(StageKind::Mix), i)); }
   const int32_t* unit_tables() const { return reinterpret_cast<const int32_t*>(descs.data() + tables_at); }
   void add_scratch(uint8_t* base);
 };
@@ -473,6 +486,11 @@ int warp_validate_one(const mxd_warp& warp, int32_t w, int32_t h);
 // Enhance operations (enhance.cpp).
 // enhances[i] against images[i] (images may be null: the entries alone).
 int enhance_validate(const mxd_image* images, const mxd_enhance* enhances, int32_t n);
+
+// ---------------------------------------------------------------------------
+// MixUp / CutMix (mix.cpp).
+// mixes[i] against images[i] and its partner's (images may be null: the entries alone).
+int mix_validate(const mxd_image* images, const mxd_mix* mixes, int32_t n);
 
 // ---------------------------------------------------------------------------
 // Formatted outputs (outfmt.cpp).

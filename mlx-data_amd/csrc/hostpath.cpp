@@ -438,11 +438,29 @@ int plan_output(HostCall& c, int32_t i, int32_t narrow_pct) {
 // ~300 ImageNet-size files a chunk, so a 128-file batch is one entropy
 // launch over the whole GPU rather than three of ~40 files on ~80 CUs
 // (round 5).
-void cut_chunks(HostCall& c) {
+// (at most 65535 images a chunk: the JPEG colour kernel puts one image per grid row)
+constexpr int32_t kChunkImages = 65535;
+// A mix call's one chunk stages every source of the call at once -- page-locked
+// host memory, the device input and the u8 scratch rows of the whole call --
+// so its staged bytes are bounded instead of cut.
+constexpr int64_t kMixChunk = (int64_t)1 << 30;
+
+int cut_chunks(HostCall& c) {
   constexpr int64_t kChunk = 24 << 20;
-  // (and at most 65535 images: the JPEG colour kernel puts one image per grid row)
-  constexpr int32_t kChunkImages = 65535;
   auto size = [&](int32_t q) { return c.st[q].pending ? c.st[q].in_size / 8 : c.st[q].in_size; };
+  // A mix call is one chunk: an image's partner must be on the device with it.
+  // Its staging then overlaps no compute.
+  if (c.ops.mixes) {
+    int64_t bytes = 0;
+    for (int32_t q = 0; q < c.n; q++) bytes += size(q);
+    if (c.n > kChunkImages || bytes > kMixChunk)
+      return fail(MXD_ERR_UNSUPPORTED, "mxd: a mix call from host sources is one chunk: at most " +
+                                           std::to_string(kChunkImages) + " images and " +
+                                           std::to_string(kMixChunk >> 20) + " MiB of staged sources (this call: " +
+                                           std::to_string(c.n) + " images, " + std::to_string(bytes >> 20) + " MiB)");
+    c.chunks.push_back({0, c.n});
+    return MXD_OK;
+  }
   for (int32_t i = 0; i < c.n;) {
     int32_t j = i;
     int64_t bytes = 0;
@@ -453,6 +471,7 @@ void cut_chunks(HostCall& c) {
     c.chunks.push_back({i, j});
     i = j;
   }
+  return MXD_OK;
 }
 
 // The output side.
@@ -676,7 +695,11 @@ int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
               const mxd_jpeg_image* jpeg, PostOps ops) {
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
   // the stages behind the resize write device destinations only
-  const char* const call = ops.warps ? "warp" : ops.enhances ? "enhance" : ops.tones ? "tone" : "colour";
+  const char* const call = ops.mixes      ? "mix"
+                           : ops.warps    ? "warp"
+                           : ops.enhances ? "enhance"
+                           : ops.tones    ? "tone"
+                                          : "colour";
   if (!dst_device && ops.per_image())
     return fail(MXD_ERR_UNSUPPORTED, std::string("mxd: ") + call + " calls need device destinations");
   mxd_out_format f32_fmt;
@@ -721,7 +744,7 @@ int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
     nnarrow += c.st[i].narrow ? 1 : 0;
   }
   if (nnarrow) g_narrow_images.fetch_add(nnarrow, std::memory_order_relaxed);
-  cut_chunks(c);
+  if (int rc = cut_chunks(c)) return rc;
 
   CtxLease lease(device);
   c.ctx = lease.ctx;

@@ -282,16 +282,21 @@ struct Members {
 };
 
 // One call for a share: the entry point of the last stage some plan has
-// (enhance, warp, tone, colour, format, plain), with the arrays of the
-// members no plan has null.
+// (mix, enhance, warp, tone, colour, format, plain), with the arrays of the
+// members no plan has null.  mixes: the share is the whole launch (partners
+// index the share's images).
 template <class Img>
-int call_abi(const Share<Img>& s, const Members& m, int32_t dtype, const mxd_out_format* of, int device, bool dst_device) {
+int call_abi(const Share<Img>& s, const Members& m, int32_t dtype, const mxd_out_format* of, int device, bool dst_device,
+             const mxd_mix* mixes = nullptr) {
   if (s.images.empty()) return MXD_OK;
   const Img* im = s.images.data();
   const int32_t n = (int32_t)s.images.size();
   const mxd_color* c = m.colored ? s.colors.data() : nullptr;
   const mxd_tone* t = m.toned ? s.tones.data() : nullptr;
   const mxd_warp* w = m.warped ? s.warps.data() : nullptr;
+  if (mixes)
+    return for_source(im, mxd_resize_crop_to_device_mix, mxd_jpeg_resize_crop_to_device_mix)(
+        im, w, m.enhanced ? s.enhances.data() : nullptr, t, c, mixes, n, dtype, of, device);
   if (m.enhanced)
     return for_source(im, mxd_resize_crop_to_device_enhance, mxd_jpeg_resize_crop_to_device_enhance)(
         im, w, s.enhances.data(), t, c, n, dtype, of, device);
@@ -306,7 +311,11 @@ int call_abi(const Share<Img>& s, const Members& m, int32_t dtype, const mxd_out
   return for_source(im, mxd_resize_crop_host, mxd_jpeg_resize_crop_host)(im, n, dtype, device);
 }
 
-int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device, const OutFormat* fmt = nullptr) {
+std::shared_ptr<void> device_block(int device, int64_t bytes);  // from the device batch pool (below)
+
+// mixes: a batch_mix launch, mixes[i] for jobs[i] (device destinations only).
+int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device, const OutFormat* fmt = nullptr,
+           const mxd_mix* mixes = nullptr) {
   g_run_calls.fetch_add(1);
   Share<mxd_image> plain;
   Share<mxd_jpeg_image> jp;
@@ -340,13 +349,53 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
   g_run_jpeg.fetch_add((int64_t)jp.images.size());
   // Per-image members and formatted outputs: device destinations only
   // (mxd_*_to_device_*); a formatted launch for host destinations is none.
-  if (const char* what = m.enhanced ? "an enhance" : m.warped ? "a warp" : m.toned ? "a tone" : m.colored ? "a colour" : nullptr) {
+  if (const char* what = mixes        ? "a mix"
+                         : m.enhanced ? "an enhance"
+                         : m.warped   ? "a warp"
+                         : m.toned    ? "a tone"
+                         : m.colored  ? "a colour"
+                                      : nullptr) {
     if (!dst_device) throw std::logic_error(std::string("mxd: ") + what + " launch needs device destinations");
   } else if (fmt && (!dst_device || n == 0)) {
     return MXD_OK;
   }
   mxd_out_format of{};
   if (fmt) of = abi_format(*fmt, jobs[0]);
+  if (mixes && n > 0) {
+    if (jp.images.empty()) return call_abi(plain, m, dtype, fmt ? &of : nullptr, device, true, mixes);
+    if (plain.images.empty()) return call_abi(jp, m, dtype, fmt ? &of : nullptr, device, true, mixes);
+    // JPEG and raw sources: a partner may be in the other C call.  Both
+    // shares run unmixed as u8 into a block of the device batch pool (dense
+    // images in batch order), then one mix call of crop-only plans over that
+    // block -- exact copies -- mixes them and writes the output form.
+    const int64_t w = jobs[0].plan.crop_w, h = jobs[0].plan.crop_h, bytes = w * h * 3;
+    std::shared_ptr<void> block = device_block(device, bytes * (int64_t)n);
+    auto* base = static_cast<uint8_t*>(block.get());
+    std::vector<mxd_image> crops(n);
+    size_t at_plain = 0, at_jpeg = 0;
+    for (size_t i = 0; i < n; i++) {
+      uint8_t* mid = base + (int64_t)i * bytes;
+      if (jobs[i].plan.src->jpeg()) {
+        jp.images[at_jpeg].dst = mid, jp.images[at_jpeg++].dst_stride = w * 3;
+      } else {
+        plain.images[at_plain].dst = mid, plain.images[at_plain++].dst_stride = w * 3;
+      }
+      mxd_image& d = crops[i];
+      d = mxd_image{};
+      d.src = mid, d.src_stride = w * 3;
+      d.src_w = d.resize_w = d.crop_w = (int32_t)w;
+      d.src_h = d.resize_h = d.crop_h = (int32_t)h;
+      d.channels = 3;
+      d.dst = jobs[i].dst, d.dst_stride = jobs[i].stride;
+    }
+    if (int rc = call_abi(jp, m, MXD_U8, nullptr, device, true)) return rc;
+    if (int rc = call_abi(plain, m, MXD_U8, nullptr, device, true)) return rc;
+    // (the two calls above are synchronous: the block is written)
+    if (int rc = mxd_resize_crop_batch_mix(crops.data(), nullptr, nullptr, nullptr, nullptr, mixes, (int32_t)n, dtype,
+                                           fmt ? &of : nullptr, device, nullptr))
+      return rc;
+    return mxd_device_synchronize(device);
+  }
   if (int rc = call_abi(jp, m, dtype, fmt ? &of : nullptr, device, dst_device)) return rc;
   return call_abi(plain, m, dtype, fmt ? &of : nullptr, device, dst_device);
 }
@@ -439,8 +488,6 @@ namespace {
 // source kind) over split_batch's slices: slice 0 on the calling thread, the
 // others on their devices' persistent workers; the first failing slice's
 // message wins.
-std::shared_ptr<void> device_block(int device, int64_t bytes);  // from the device batch pool (below)
-
 // Results that only a device call can write, bound for host memory -- the
 // formatted outputs (the _fmt calls) and every output of a colour launch (the
 // _color calls) have device destinations only: the jobs run into a block of
@@ -450,7 +497,8 @@ std::shared_ptr<void> device_block(int device, int64_t bytes);  // from the devi
 // (rows copied out to each job's stride).  fmt == nullptr: dtype's form (u8 /
 // f32).  No chunk overlap between the kernels and the copy.  Returns the error
 // message, empty when all went well.
-std::string run_formatted_to_host(const Job* jobs, size_t n, int device, int32_t dtype, const OutFormat* fmt) {
+std::string run_formatted_to_host(const Job* jobs, size_t n, int device, int32_t dtype, const OutFormat* fmt,
+                                  const mxd_mix* mixes = nullptr) {
   if (n == 0) return std::string();
   try {
     const int64_t es = fmt ? (fmt->elem == MXD_ELEM_F32 ? 4 : 2) : dtype == MXD_F32_DIV255 ? 4 : 1;
@@ -479,7 +527,7 @@ std::string run_formatted_to_host(const Job* jobs, size_t n, int device, int32_t
       dev[i].stride = row[i];
       at += bytes[i];
     }
-    if (run_on(dev.data(), n, dtype, device, true, fmt) != MXD_OK) return mxd_last_error();
+    if (run_on(dev.data(), n, dtype, device, true, fmt, mixes) != MXD_OK) return mxd_last_error();
     if (dense) {
       if (mxd_memcpy_d2h(lo, base, (size_t)sum, device) != MXD_OK) return mxd_last_error();
     } else if (packed) {
@@ -1930,9 +1978,136 @@ std::shared_ptr<Array> batch_arrays(const std::vector<std::shared_ptr<Array>>& a
   return res;
 }
 
+// ------------------------------------------------------------------ batch_mix
+void check_mix_spec(const MixSpec& s) {
+  auto bad = [](const std::string& msg) { throw std::invalid_argument("batch_mix: " + msg); };
+  if (!(std::isfinite(s.mixup_alpha) && s.mixup_alpha >= 0.0)) bad("mixup_alpha must be finite and >= 0");
+  if (!(std::isfinite(s.cutmix_alpha) && s.cutmix_alpha >= 0.0)) bad("cutmix_alpha must be finite and >= 0");
+  if (s.mixup_alpha == 0.0 && s.cutmix_alpha == 0.0) bad("one of mixup_alpha and cutmix_alpha must be > 0");
+  if (!(s.prob >= 0.0 && s.prob <= 1.0)) bad("prob must be in 0..1");
+  if (!(s.switch_prob >= 0.0 && s.switch_prob <= 1.0)) bad("switch_prob must be in 0..1");
+  if (s.lam_key.empty() || s.partner_key.empty()) bad("lam_key and partner_key must not be empty");
+  if (s.lam_key == s.partner_key || s.lam_key == s.key || s.partner_key == s.key)
+    bad("key, lam_key and partner_key must differ");
+}
+
+std::vector<MixDraw> batch_mix_draws(int64_t n, int64_t h, int64_t w, const MixSpec& spec) {
+  check_mix_spec(spec);
+  if (n < 0 || h <= 0 || w <= 0) throw std::invalid_argument("batch_mix: bad batch or image size");
+  auto st = get_state();
+  std::mt19937& gen = st->gen;
+  auto uniform = [&gen] { return std::uniform_real_distribution<double>(0.0, 1.0)(gen); };
+  auto clampi = [](int64_t v, int64_t hi) { return (int32_t)std::min<int64_t>(std::max<int64_t>(v, 0), hi); };
+  // One draw set: the entry without its partner.
+  auto draw = [&]() {
+    MixDraw d{};
+    d.lam = 1.0f;
+    if (!(uniform() < spec.prob)) return d;
+    bool cut = spec.cutmix_alpha > 0.0;
+    if (spec.mixup_alpha > 0.0 && spec.cutmix_alpha > 0.0) cut = uniform() < spec.switch_prob;
+    const double alpha = cut ? spec.cutmix_alpha : spec.mixup_alpha;
+    double lam;
+    if (alpha == 1.0) {
+      lam = uniform();
+    } else {
+      const double g1 = std::gamma_distribution<double>(alpha, 1.0)(gen);
+      const double g2 = std::gamma_distribution<double>(alpha, 1.0)(gen);
+      lam = g1 + g2 > 0.0 ? g1 / (g1 + g2) : 0.5;  // (two underflowed draws of a tiny alpha)
+    }
+    if (!cut) {
+      d.mix.op = MXD_MIX_MIXUP;
+      d.mix.w_self = (float)lam;
+      d.mix.w_other = (float)(1.0 - lam);
+      d.lam = (float)lam;
+      return d;
+    }
+    const double ratio = std::sqrt(1.0 - lam);
+    const int64_t cut_h = (int64_t)((double)h * ratio), cut_w = (int64_t)((double)w * ratio);
+    const int64_t cy = std::uniform_int_distribution<int>(0, (int)h - 1)(gen);
+    const int64_t cx = std::uniform_int_distribution<int>(0, (int)w - 1)(gen);
+    d.mix.op = MXD_MIX_CUTMIX;
+    d.mix.y0 = clampi(cy - cut_h / 2, h), d.mix.y1 = clampi(cy + cut_h / 2, h);
+    d.mix.x0 = clampi(cx - cut_w / 2, w), d.mix.x1 = clampi(cx + cut_w / 2, w);
+    d.lam = (float)(1.0 - (double)((int64_t)(d.mix.y1 - d.mix.y0) * (d.mix.x1 - d.mix.x0)) / (double)(h * w));
+    return d;
+  };
+  std::vector<MixDraw> out((size_t)n);
+  const int64_t sets = spec.mode == MixMode::Batch ? std::min<int64_t>(n, 1) : spec.mode == MixMode::Pair ? (n + 1) / 2 : n;
+  for (int64_t k = 0; k < sets; k++) {
+    const MixDraw d = draw();
+    if (spec.mode == MixMode::Batch) {
+      for (auto& o : out) o = d;
+    } else {
+      out[(size_t)k] = d;
+      if (spec.mode == MixMode::Pair) out[(size_t)(n - 1 - k)] = d;
+    }
+  }
+  for (int64_t i = 0; i < n; i++) {
+    mxd_mix& m = out[(size_t)i].mix;
+    m.partner = (int32_t)(m.op == MXD_MIX_NONE ? i : n - 1 - i);
+  }
+  return out;
+}
+
+namespace {
+// batch_arrays for the key batch_mix mixes: every array a pending image plan
+// of 3 channels and one crop size, batched by one launch that mixes image i
+// with image draws[i].mix.partner.  The batch is never split over devices: a
+// partner must be in the same call.
+std::shared_ptr<Array> batch_mix_arrays(const std::string& key, const std::vector<std::shared_ptr<Array>>& arrs,
+                                        const std::vector<MixDraw>& draws, int device) {
+  auto bad = [&key](const std::string& msg) { throw std::runtime_error("batch_mix: key <" + key + ">: " + msg); };
+  const auto type = arrs.front()->type();
+  const OutFormat* fmt = batch_format(arrs);
+  std::vector<Job> jobs;
+  std::vector<mxd_mix> mixes;
+  for (size_t i = 0; i < arrs.size(); i++) {
+    const auto& a = arrs[i];
+    const std::string at = "sample " + std::to_string(i) + " ";
+    if (a->device() >= 0) bad(at + "is a device-resident array");
+    if (a->ndim() == 4) bad(at + "is a video");
+    if (a->ndim() != 3 || !deferred(*a)) bad(at + "is a materialised array, not a pending image");
+    if (a->type() != type) bad(at + "has another type than sample 0");
+    ImagePlan p = deferred_plan(a);
+    if (p.channels() != 3) bad(at + "has " + std::to_string(p.channels()) + " channels, not 3");
+    if (!jobs.empty() && (p.crop_w != jobs[0].plan.crop_w || p.crop_h != jobs[0].plan.crop_h))
+      bad(at + "is " + std::to_string(p.crop_w) + " x " + std::to_string(p.crop_h) + ", sample 0 " +
+          std::to_string(jobs[0].plan.crop_w) + " x " + std::to_string(jobs[0].plan.crop_h) + " (a ragged batch)");
+    jobs.push_back(Job{std::move(p), nullptr, 0});
+    mixes.push_back(draws[i].mix);
+  }
+  const int64_t n = (int64_t)arrs.size(), isz = itemsize(type);
+  std::vector<int64_t> bshape{n};
+  bshape.insert(bshape.end(), arrs.front()->shape().begin(), arrs.front()->shape().end());
+  const int64_t item = shape_size(arrs.front()->shape()) * isz;
+  // rows: W x C elements in (H, W, C); W elements in the planes of (C, H, W)
+  const int64_t row = (fmt && fmt->chw() ? jobs[0].plan.crop_w : jobs[0].plan.crop_w * 3) * isz;
+  const std::vector<int> devs = devices();
+  if (devs.empty()) throw std::runtime_error("mxd: no HIP device visible (the image path runs only on the GPU)");
+  std::shared_ptr<Array> res;
+  if (device >= 0) {
+    res = std::make_shared<Array>(type, bshape, device_pool().get(device, item * n), device);
+  } else {
+    res = std::make_shared<Array>(type, bshape, alloc_batch_bytes(item * n));
+  }
+  auto* base = static_cast<uint8_t*>(res->data());
+  for (int64_t i = 0; i < n; i++) jobs[(size_t)i].dst = base + i * item, jobs[(size_t)i].stride = row;
+  const int32_t dtype = fmt ? MXD_U8 : out_dtype(type);
+  if (device >= 0) {
+    check(run_on(jobs.data(), jobs.size(), dtype, device, true, fmt, mixes.data()));
+  } else {
+    // whole to one device, consecutive batches rotating like small batches
+    const int on = devs[g_rr.fetch_add(1) % devs.size()];
+    const std::string err = run_formatted_to_host(jobs.data(), jobs.size(), on, dtype, fmt, mixes.data());
+    if (!err.empty()) throw std::runtime_error(err);
+  }
+  return res;
+}
+}  // namespace
+
 // core::merge_batch (core/Utils.cpp:209-252)
 Sample merge_batch(const std::vector<Sample>& samples, const std::unordered_map<std::string, double>& pad,
-                   const std::unordered_map<std::string, int>& dims, const DeviceOut& dev) {
+                   const std::unordered_map<std::string, int>& dims, const DeviceOut& dev, const MixSpec* mix) {
   std::vector<std::string> keys;
   std::vector<std::vector<std::shared_ptr<Array>>> values;
   for (const auto& s : samples) {
@@ -1947,6 +2122,8 @@ Sample merge_batch(const std::vector<Sample>& samples, const std::unordered_map<
       values[k].push_back(it->second);
     }
   }
+  if (mix && std::find(keys.begin(), keys.end(), mix->key) == keys.end())
+    throw std::runtime_error("batch_mix: key <" + mix->key + "> is not in the samples");
   Sample out;
   for (size_t k = 0; k < keys.size(); k++) {
     auto p = pad.find(keys[k]);
@@ -1959,6 +2136,26 @@ Sample merge_batch(const std::vector<Sample>& samples, const std::unordered_map<
       else
         on = std::find(dev.keys.begin(), dev.keys.end(), keys[k]) != dev.keys.end();
       device = on ? dev.device : -1;
+    }
+    if (mix && keys[k] == mix->key) {
+      if (d != dims.end()) throw std::runtime_error("batch_mix: key <" + mix->key + ">: no dim for the mixed key");
+      const auto& first = values[k].front();
+      if (first->ndim() != 3 || !deferred(*first))
+        throw std::runtime_error("batch_mix: key <" + mix->key + ">: sample 0 is " +
+                                 (first->ndim() == 4 ? "a video" : "a materialised array, not a pending image"));
+      const ImagePlan p0 = deferred_plan(first);
+      const std::vector<MixDraw> draws = batch_mix_draws((int64_t)values[k].size(), p0.crop_h, p0.crop_w, *mix);
+      out[keys[k]] = batch_mix_arrays(mix->key, values[k], draws, dev.device >= 0 ? device : -1);
+      const int64_t n = (int64_t)draws.size();
+      auto lam = std::make_shared<Array>(DType::Float, std::vector<int64_t>{n}, alloc_bytes(n * 4));
+      auto partner = std::make_shared<Array>(DType::Int64, std::vector<int64_t>{n}, alloc_bytes(n * 8));
+      for (int64_t i = 0; i < n; i++) {
+        static_cast<float*>(lam->data())[i] = draws[(size_t)i].lam;
+        static_cast<int64_t*>(partner->data())[i] = draws[(size_t)i].mix.partner;
+      }
+      out[mix->lam_key] = lam;
+      out[mix->partner_key] = partner;
+      continue;
     }
     out[keys[k]] = batch_arrays(values[k], p == pad.end() ? 0.0 : p->second, d == dims.end() ? 0 : d->second,
                                 d != dims.end(), device);
@@ -2059,8 +2256,9 @@ Sample BufferTransform::get(int64_t idx) const {
 
 // buffer/Batch.cpp:10-25,52-68
 BufferBatch::BufferBatch(std::shared_ptr<Buffer> b, int64_t batch_size, std::unordered_map<std::string, double> pad,
-                         std::unordered_map<std::string, int> dims, DeviceOut out)
-    : b_(std::move(b)), bs_(batch_size), pad_(std::move(pad)), dims_(std::move(dims)), out_(std::move(out)) {
+                         std::unordered_map<std::string, int> dims, DeviceOut out, std::shared_ptr<const MixSpec> mix)
+    : b_(std::move(b)), bs_(batch_size), pad_(std::move(pad)), dims_(std::move(dims)), out_(std::move(out)),
+      mix_(std::move(mix)) {
   if (bs_ <= 0) throw std::runtime_error("Batch: batch size must be positive");
   size_ = (b_->size() + bs_ - 1) / bs_;
 }
@@ -2070,7 +2268,7 @@ Sample BufferBatch::get(int64_t idx) const {
   const int64_t n = std::min(bs_, b_->size() - idx * bs_);
   std::vector<Sample> samples(n);
   for (int64_t i = 0; i < n; i++) samples[i] = b_->get(idx * bs_ + i);
-  return merge_batch(samples, pad_, dims_, out_);
+  return merge_batch(samples, pad_, dims_, out_, mix_.get());
 }
 
 // ------------------------------------------------------------------ streams
@@ -2104,8 +2302,9 @@ Sample StreamTransform::next() const {
 
 // stream/Batch.cpp:10-39
 StreamBatch::StreamBatch(std::shared_ptr<Stream> s, int64_t batch_size, std::unordered_map<std::string, double> pad,
-                         std::unordered_map<std::string, int> dims, DeviceOut out)
-    : s_(std::move(s)), bs_(batch_size), pad_(std::move(pad)), dims_(std::move(dims)), out_(std::move(out)) {
+                         std::unordered_map<std::string, int> dims, DeviceOut out, std::shared_ptr<const MixSpec> mix)
+    : s_(std::move(s)), bs_(batch_size), pad_(std::move(pad)), dims_(std::move(dims)), out_(std::move(out)),
+      mix_(std::move(mix)) {
   if (bs_ <= 0) throw std::runtime_error("Batch: batch size must be positive");
 }
 
@@ -2120,7 +2319,7 @@ Sample StreamBatch::next() const {
     }
   }
   PipeTimer timer(3);
-  return samples.empty() ? Sample() : merge_batch(samples, pad_, dims_, out_);
+  return samples.empty() ? Sample() : merge_batch(samples, pad_, dims_, out_, mix_.get());
 }
 
 // stream/Prefetch.cpp:9-66

@@ -30,6 +30,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "mxd_amd.h"
+
 namespace mxd {
 namespace pipe {
 
@@ -554,8 +556,37 @@ struct DeviceOut {
   int device = -1;
   std::vector<std::string> keys;
 };
+// batch_mix: MixUp / CutMix across the images of `key` in a batch (timm's
+// FastCollateMixup).  The partner of image i of n is
+// n - 1 - i.  mode: one draw set per batch, per pair (i < ceil(n / 2), shared by
+// both members) or per image.
+enum class MixMode : int { Batch = 0, Pair = 1, Elem = 2 };
+struct MixSpec {
+  std::string key, lam_key = "mix_lam", partner_key = "mix_partner";
+  double mixup_alpha = 0.0, cutmix_alpha = 0.0, prob = 1.0, switch_prob = 0.5;
+  MixMode mode = MixMode::Batch;
+};
+// Throws std::invalid_argument (the op's ValueError) for a spec no batch could run.
+void check_mix_spec(const MixSpec& spec);
+// What one image of a batch gets: the C ABI's entry and the weight of its own label.
+struct MixDraw {
+  mxd_mix mix;
+  float lam;  // 1 for MXD_MIX_NONE; CutMix: 1 - box area / (h w)
+};
+// The entries of a batch of n images of h x w pixels, drawn from the calling
+// thread's State.  Per draw set, with freshly constructed distributions:
+// uniform_real<double>(0, 1), the set is applied iff it is < prob (nothing more
+// is drawn otherwise); with both alphas > 0 one more, CutMix iff it is <
+// switch_prob; lam, one uniform_real<double>(0, 1) for alpha == 1, else
+// g1 / (g1 + g2) of two gamma_distribution<double>(alpha, 1) draws; for CutMix
+// timm's rand_bbox without margin: cy = uniform_int<int>(0, h - 1), then cx.
+std::vector<MixDraw> batch_mix_draws(int64_t n, int64_t h, int64_t w, const MixSpec& spec);
+
+// mix: the arrays of mix->key are mixed (batch_mix) and the sample gains
+// mix->lam_key (float32 (B,)) and mix->partner_key (int64 (B,)).
 Sample merge_batch(const std::vector<Sample>& samples, const std::unordered_map<std::string, double>& pad,
-                   const std::unordered_map<std::string, int>& dims, const DeviceOut& out = {});
+                   const std::unordered_map<std::string, int>& dims, const DeviceOut& out = {},
+                   const MixSpec* mix = nullptr);
 
 // ---------------------------------------------------------------- threads
 // Workers share the queue state with the pool, so the pool may be destroyed
@@ -626,7 +657,7 @@ class BufferTransform : public Buffer {
 class BufferBatch : public Buffer {
  public:
   BufferBatch(std::shared_ptr<Buffer> b, int64_t batch_size, std::unordered_map<std::string, double> pad,
-              std::unordered_map<std::string, int> dims, DeviceOut out = {});
+              std::unordered_map<std::string, int> dims, DeviceOut out = {}, std::shared_ptr<const MixSpec> mix = nullptr);
   int64_t size() const override { return size_; }
   Sample get(int64_t idx) const override;
 
@@ -636,6 +667,7 @@ class BufferBatch : public Buffer {
   std::unordered_map<std::string, double> pad_;
   std::unordered_map<std::string, int> dims_;
   DeviceOut out_;
+  std::shared_ptr<const MixSpec> mix_;  // batch_mix
 };
 
 // ---------------------------------------------------------------- streams
@@ -672,7 +704,7 @@ class StreamTransform : public Stream {
 class StreamBatch : public Stream {
  public:
   StreamBatch(std::shared_ptr<Stream> s, int64_t batch_size, std::unordered_map<std::string, double> pad,
-              std::unordered_map<std::string, int> dims, DeviceOut out = {});
+              std::unordered_map<std::string, int> dims, DeviceOut out = {}, std::shared_ptr<const MixSpec> mix = nullptr);
   Sample next() const override;
   void reset() override { s_->reset(); }
 
@@ -682,6 +714,7 @@ class StreamBatch : public Stream {
   std::unordered_map<std::string, double> pad_;
   std::unordered_map<std::string, int> dims_;
   DeviceOut out_;
+  std::shared_ptr<const MixSpec> mix_;  // batch_mix
 };
 
 class Prefetch : public Stream {

@@ -669,6 +669,21 @@ DeviceOut device_out(const py::object& device, const py::object& keys) {
   return o;
 }
 
+// batch_mix's keyword arguments as a checked MixSpec (ValueError when the op is made).
+std::shared_ptr<const MixSpec> mix_spec(const std::string& key, double mixup_alpha, double cutmix_alpha, double prob,
+                                        double switch_prob, const std::string& mode, const std::string& lam_key,
+                                        const std::string& partner_key) {
+  auto s = std::make_shared<MixSpec>();
+  s->key = key, s->lam_key = lam_key, s->partner_key = partner_key;
+  s->mixup_alpha = mixup_alpha, s->cutmix_alpha = cutmix_alpha, s->prob = prob, s->switch_prob = switch_prob;
+  if (mode == "batch") s->mode = MixMode::Batch;
+  else if (mode == "pair") s->mode = MixMode::Pair;
+  else if (mode == "elem") s->mode = MixMode::Elem;
+  else throw std::invalid_argument("batch_mix: unknown mode '" + mode + "' (batch, pair, elem)");
+  check_mix_spec(*s);
+  return s;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_pipeline, m) {
@@ -740,6 +755,20 @@ PYBIND11_MODULE(_pipeline, m) {
           py::arg("batch_size"), py::arg("pad") = PadMap{}, py::arg("dim") = DimMap{}, py::arg("device") = py::none(),
           py::arg("device_keys") = py::none())
       .def(
+          "batch_mix",
+          [](const std::shared_ptr<Buffer>& b, int64_t batch_size, const std::string& key, double mixup_alpha,
+             double cutmix_alpha, double prob, double switch_prob, const std::string& mode, const std::string& lam_key,
+             const std::string& partner_key, PadMap pad, DimMap dim, py::object device,
+             py::object device_keys) -> std::shared_ptr<Buffer> {
+            auto spec = mix_spec(key, mixup_alpha, cutmix_alpha, prob, switch_prob, mode, lam_key, partner_key);
+            return std::make_shared<BufferBatch>(b, batch_size, std::move(pad), std::move(dim),
+                                                 device_out(device, device_keys), std::move(spec));
+          },
+          py::arg("batch_size"), py::arg("key"), py::kw_only(), py::arg("mixup_alpha") = 0.0,
+          py::arg("cutmix_alpha") = 0.0, py::arg("prob") = 1.0, py::arg("switch_prob") = 0.5, py::arg("mode") = "batch",
+          py::arg("lam_key") = "mix_lam", py::arg("partner_key") = "mix_partner", py::arg("pad") = PadMap{},
+          py::arg("dim") = DimMap{}, py::arg("device") = py::none(), py::arg("device_keys") = py::none())
+      .def(
           "ordered_prefetch",
           [](const std::shared_ptr<Buffer>& b, int prefetch_size, int num_threads) -> std::shared_ptr<Stream> {
             return nogil_owned<Stream>(new OrderedPrefetch(b, prefetch_size, num_threads));
@@ -771,6 +800,20 @@ PYBIND11_MODULE(_pipeline, m) {
           py::arg("batch_size"), py::arg("pad") = PadMap{}, py::arg("dim") = DimMap{}, py::arg("device") = py::none(),
           py::arg("device_keys") = py::none())
       .def(
+          "batch_mix",
+          [](const std::shared_ptr<Stream>& s, int64_t batch_size, const std::string& key, double mixup_alpha,
+             double cutmix_alpha, double prob, double switch_prob, const std::string& mode, const std::string& lam_key,
+             const std::string& partner_key, PadMap pad, DimMap dim, py::object device,
+             py::object device_keys) -> std::shared_ptr<Stream> {
+            auto spec = mix_spec(key, mixup_alpha, cutmix_alpha, prob, switch_prob, mode, lam_key, partner_key);
+            return std::make_shared<StreamBatch>(s, batch_size, std::move(pad), std::move(dim),
+                                                 device_out(device, device_keys), std::move(spec));
+          },
+          py::arg("batch_size"), py::arg("key"), py::kw_only(), py::arg("mixup_alpha") = 0.0,
+          py::arg("cutmix_alpha") = 0.0, py::arg("prob") = 1.0, py::arg("switch_prob") = 0.5, py::arg("mode") = "batch",
+          py::arg("lam_key") = "mix_lam", py::arg("partner_key") = "mix_partner", py::arg("pad") = PadMap{},
+          py::arg("dim") = DimMap{}, py::arg("device") = py::none(), py::arg("device_keys") = py::none())
+      .def(
           "prefetch",
           [](const std::shared_ptr<Stream>& s, int prefetch_size, int num_threads) -> std::shared_ptr<Stream> {
             return nogil_owned<Stream>(new Prefetch(s, prefetch_size, num_threads));
@@ -789,6 +832,21 @@ PYBIND11_MODULE(_pipeline, m) {
 
   m.def("set_state", &set_state, py::arg("seed") = 1234);
   m.def("set_devices", &set_devices, py::arg("devices"));
+  // diagnostics (device-free): the entries batch_mix would give a batch of n images of h x w pixels, drawn
+  // from the calling thread's State: (op, partner, w_self, w_other, x0, y0, x1, y1, lam) per image
+  m.def(
+      "_batch_mix_draws",
+      [](int64_t n, int64_t h, int64_t w, double mixup_alpha, double cutmix_alpha, double prob, double switch_prob,
+         const std::string& mode) {
+        auto spec = mix_spec("image", mixup_alpha, cutmix_alpha, prob, switch_prob, mode, "mix_lam", "mix_partner");
+        std::vector<std::tuple<int, int, float, float, int, int, int, int, float>> out;
+        for (const MixDraw& d : batch_mix_draws(n, h, w, *spec))
+          out.emplace_back(d.mix.op, d.mix.partner, d.mix.w_self, d.mix.w_other, d.mix.x0, d.mix.y0, d.mix.x1, d.mix.y1,
+                           d.lam);
+        return out;
+      },
+      py::arg("n"), py::arg("h"), py::arg("w"), py::kw_only(), py::arg("mixup_alpha") = 0.0, py::arg("cutmix_alpha") = 0.0,
+      py::arg("prob") = 1.0, py::arg("switch_prob") = 0.5, py::arg("mode") = "batch");
   // diagnostics: how a batch of n images is split over ndev devices
   m.def(
       "_split_batch",

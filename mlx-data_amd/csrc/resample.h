@@ -280,6 +280,30 @@ struct EnhanceRowDev {
 };
 static_assert(sizeof(EnhanceRowDev) == 56, "EnhanceRowDev layout");
 int launch_enhance(const EnhanceRowDev* rows, int nimgs, int ntiles, void* stream);
+// The mix stage (mix.hip): the last stage of a mix call (mxd_mix), over u8 RGB
+// scratch rows.  One entry per image; a workgroup takes kMixRows rows of one
+// image, workgroups numbered through blk_begin.  It reads the image's rows
+// and, unless the op is NONE, its partner's rows -- both written by the stage
+// before it, so no image reads a mixed byte -- and writes the destinations in
+// the call's output form (fmt as pixel_rows takes it: table == nullptr is u8).
+constexpr int kMixRows = 8;
+// mxd_mix_op's values.
+enum MixOp : int32_t { kMixNone = 0, kMixMixup = 1, kMixCutmix = 2 };
+struct MixRowDev {
+  const uint8_t* src;  // u8 rows (16-byte aligned base, stride a multiple of 16)
+  void* dst;           // the caller's destination (any alignment)
+  int64_t src_stride, dst_stride;
+  int32_t w, h;
+  const uint8_t* psrc;  // the partner's rows among those the stage reads (null for kMixNone)
+  int64_t psrc_stride;
+  int32_t blk_begin;    // first of the image's workgroups among the launch's
+  int32_t op;           // MixOp
+  float w_self, w_other;   // kMixMixup (0 otherwise)
+  int32_t x0, y0, x1, y1;  // kMixCutmix (0 otherwise)
+  int32_t pad[2];
+};
+static_assert(sizeof(MixRowDev) == 96, "MixRowDev layout");
+int launch_mix(const MixRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
 // What the entries of every stage behind the resize begin with: the rows the
 // stage reads and writes.  The host places them by one rule for all stages
 // (capi_internal.h, the stage chain); the rest of an entry is its stage's own.
@@ -299,6 +323,7 @@ struct RowHead {
 MXD_ROW_HEAD(FmtRowDev, crop_w, crop_h);
 MXD_ROW_HEAD(WarpRowDev, w, h);
 MXD_ROW_HEAD(EnhanceRowDev, w, h);
+MXD_ROW_HEAD(MixRowDev, w, h);
 #undef MXD_ROW_HEAD
 // Waves of this configuration the device runs at once (occupancy x CUs), 0 if unknown.
 int wave_capacity(const WaveCfg& cfg, int device);

@@ -50,6 +50,8 @@ EXPORTS = (
     "mxd_jpeg_resize_crop_to_device_warp",
     "mxd_enhance_validate", "mxd_enhance_apply_u8", "mxd_resize_crop_batch_enhance",
     "mxd_resize_crop_to_device_enhance", "mxd_jpeg_resize_crop_to_device_enhance",
+    "mxd_mix_validate", "mxd_mix_apply_u8", "mxd_resize_crop_batch_mix", "mxd_resize_crop_to_device_mix",
+    "mxd_jpeg_resize_crop_to_device_mix",
 )
 
 MXD_ELEM_F32 = 0
@@ -524,6 +526,88 @@ def jpeg_resize_crop_to_device_enhance(images, warps, enhances, tones, colors, n
                                        device=0):
     check(lib().mxd_jpeg_resize_crop_to_device_enhance(images, warps, enhances, tones, colors, n, out_dtype,
                                                        _fmt_ref(fmt), device))
+
+
+MXD_MIX_NONE = 0
+MXD_MIX_MIXUP = 1
+MXD_MIX_CUTMIX = 2
+
+
+class MxdMix(ctypes.Structure):
+    """struct mxd_mix (include/mxd_amd.h): an op, the partner's index, MixUp's two weights,
+    CutMix's box, two reserved words (0)."""
+
+    _fields_ = [("op", ctypes.c_int32), ("partner", ctypes.c_int32), ("w_self", ctypes.c_float),
+                ("w_other", ctypes.c_float), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32),
+                ("y1", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+def mixup(partner, lam):
+    """The MixUp entry of a Python-float lam: w_self = (float)lam, w_other = (float)(1.0 - lam)."""
+    return (MXD_MIX_MIXUP, int(partner), float(lam), 1.0 - float(lam))
+
+
+def cutmix(partner, x0, y0, x1, y1):
+    """The CutMix entry of the box [x0, x1) x [y0, y1)."""
+    return (MXD_MIX_CUTMIX, int(partner), int(x0), int(y0), int(x1), int(y1))
+
+
+def make_mixes(mixes):
+    """Entries -> ctypes array of mxd_mix.  An entry is an MxdMix, (MXD_MIX_NONE,),
+    (MXD_MIX_MIXUP, partner, w_self, w_other) or (MXD_MIX_CUTMIX, partner, x0, y0, x1, y1);
+    mixup() and cutmix() make the last two."""
+    arr = (MxdMix * max(1, len(mixes)))()
+    for i, m in enumerate(mixes):
+        if isinstance(m, MxdMix):
+            arr[i] = m
+            continue
+        arr[i].op = int(m[0])
+        if len(m) > 1:
+            arr[i].partner = int(m[1])
+        if arr[i].op == MXD_MIX_CUTMIX:
+            arr[i].x0, arr[i].y0, arr[i].x1, arr[i].y1 = (int(v) for v in m[2:6])
+        elif len(m) > 2:
+            arr[i].w_self, arr[i].w_other = float(m[2]), float(m[3])
+    return arr
+
+
+def mix_validate(images, mixes, n=None):
+    """mxd_mix_validate: mixes (entries as make_mixes takes them) against an mxd_image array, or None."""
+    check(lib().mxd_mix_validate(images, make_mixes(mixes), len(mixes) if n is None else n))
+
+
+def mix_apply_u8(own, partner, mix, out=None):
+    """mxd_mix_apply_u8: the CPU statement of a mix on two (h, w, 3) uint8 images (any row
+    stride); partner may be None for MXD_MIX_NONE.  out: an (h, w, 3) uint8 array (default: a new one)."""
+    assert own.dtype == np.uint8 and own.ndim == 3 and own.shape[2] == 3 and own.strides[1:] == (3, 1)
+    if partner is not None:
+        assert partner.dtype == np.uint8 and partner.shape == own.shape and partner.strides[1:] == (3, 1)
+    h, w = own.shape[:2]
+    if out is None:
+        out = np.empty((h, w, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.shape == own.shape and out.strides[1:] == (3, 1)
+    check(lib().mxd_mix_apply_u8(ctypes.c_void_p(own.ctypes.data), ctypes.c_int64(own.strides[0]),
+                                 ctypes.c_void_p(partner.ctypes.data if partner is not None else None),
+                                 ctypes.c_int64(partner.strides[0] if partner is not None else 0), w, h,
+                                 make_mixes([mix]), ctypes.c_void_p(out.ctypes.data), ctypes.c_int64(out.strides[0])))
+    return out
+
+
+def resize_crop_batch_mix(images, warps, enhances, tones, colors, mixes, n, out_dtype=MXD_U8, fmt=None, device=0,
+                          stream=None):
+    check(lib().mxd_resize_crop_batch_mix(images, warps, enhances, tones, colors, mixes, n, out_dtype, _fmt_ref(fmt),
+                                          device, ctypes.c_void_p(stream)))
+
+
+def resize_crop_to_device_mix(images, warps, enhances, tones, colors, mixes, n, out_dtype=MXD_U8, fmt=None, device=0):
+    check(lib().mxd_resize_crop_to_device_mix(images, warps, enhances, tones, colors, mixes, n, out_dtype,
+                                              _fmt_ref(fmt), device))
+
+
+def jpeg_resize_crop_to_device_mix(images, warps, enhances, tones, colors, mixes, n, out_dtype=MXD_U8, fmt=None,
+                                   device=0):
+    check(lib().mxd_jpeg_resize_crop_to_device_mix(images, warps, enhances, tones, colors, mixes, n, out_dtype,
+                                                   _fmt_ref(fmt), device))
 
 
 def set_kernel_policy(policy):

@@ -148,6 +148,16 @@ colour (``csrc/jpegdev.hip``) -- before resizing, with the same bytes;
 progressive and other files are entropy-decoded on the host first.
 ``set_device_entropy(False)`` keeps the Huffman decode on the host for every
 file, ``set_device_decode(False)`` decodes whole on the host.
+
+``batch_mix(batch_size, key, mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0,
+switch_prob=0.5, mode="batch", lam_key="mix_lam", partner_key="mix_partner",
+...)`` batches like ``batch`` and runs MixUp / CutMix (timm's
+``FastCollateMixup``) across the images of ``key`` inside the same launch:
+image ``i`` is mixed with image ``n - 1 - i``, ``lam`` and the boxes are drawn
+per batch, pair or element from the thread's state, and the batch gains the
+weight of each sample's own label and its partner's index.  The images must
+be pending RGB images of one crop size; ``image_to_float`` /
+``image_normalize`` compose.
 Other formats go to a Pillow hook that follows the reference's stb_image
 rules (``core/image/ImageSTBI.cpp``: 1/2/3 channels kept, 4 -> 3, 16-bit >> 8).
 """
