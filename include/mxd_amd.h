@@ -75,7 +75,9 @@ extern "C" {
  * 7, added without a new number (test for MXD_HAS_MIX / the symbols): MixUp
  * and CutMix across the images of a call -- mxd_mix_op, mxd_mix,
  * mxd_mix_validate, mxd_mix_apply_u8, mxd_resize_crop_batch_mix,
- * mxd_resize_crop_to_device_mix, mxd_jpeg_resize_crop_to_device_mix. */
+ * mxd_resize_crop_to_device_mix, mxd_jpeg_resize_crop_to_device_mix.
+ * 7, added without a new number (test for MXD_HAS_GAUSSIAN_BLUR / the
+ * symbols): the enhance op MXD_ENHANCE_GAUSSIAN_BLUR and mxd_gaussian_weights. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
@@ -83,6 +85,7 @@ extern "C" {
 #define MXD_HAS_WARP 1
 #define MXD_HAS_ENHANCE 1
 #define MXD_HAS_MIX 1
+#define MXD_HAS_GAUSSIAN_BLUR 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -748,19 +751,39 @@ int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_
  * trunc(x) for 0 <= f <= 1, else 0 for x <= 0, 255 for x >= 255, trunc(x)
  * between: MXD_TONE_CONTRAST's rule.  Factor 1 returns q, factor 0 returns D.
  *
+ * GAUSSIAN_BLUR is not a blend.  It is a true separable Gaussian with
+ * torchvision's kernel and padding (transforms.GaussianBlur, the blur of the
+ * SimCLR / BYOL / MoCo v3 / DINO recipes) -- not Pillow's box-blur
+ * approximation of ImageFilter.GaussianBlur.  factor is sigma, reserved[0] the
+ * kernel size k (odd, 3..33), R = (k - 1) / 2.  The weights are
+ * mxd_gaussian_weights' (below).  Padding is torch / NumPy "reflect": the
+ * mirror without repeating the edge, repeated for any radius with period
+ * 2 (n - 1); index 0 for n == 1.  The horizontal pass runs first, then the
+ * vertical one; every operation is a correctly rounded float32 operation and
+ * none is fused; both passes use the symmetric form
+ *
+ *   H  a = w[R] (float)q(x); for d = 1..R in order
+ *      a = a + w[R+d] (float)(q(x-d) + q(x+d))      the byte sum in integers
+ *   V  the same over the float32 H results; h(y-d) + h(y+d) is a float32 add
+ *
+ * and the result is rint(a) (half to even) clamped to 0..255.  The symmetric
+ * form makes the blur of a mirrored image the mirror of the blur, bit for bit.
+ *
  * In a call the stage order is geometry, warp, enhance, tone, colour, output
  * form: the tone statistics are those of the enhanced bytes. */
 enum mxd_enhance_op {
   MXD_ENHANCE_NONE = 0,
   MXD_ENHANCE_SHARPNESS = 1,
   MXD_ENHANCE_COLOR = 2,
-  MXD_ENHANCE_BRIGHTNESS = 3
+  MXD_ENHANCE_BRIGHTNESS = 3,
+  /* (4 to 7 are not assigned) */
+  MXD_ENHANCE_GAUSSIAN_BLUR = 8
 };
 
 typedef struct mxd_enhance {
   int32_t op;          /* mxd_enhance_op; NONE: the image's bytes stay as they are, factor is not read */
-  float factor;        /* f: finite, 0 <= f <= 1e6 */
-  int32_t reserved[2]; /* must be 0 */
+  float factor;        /* f: finite, 0 <= f <= 1e6; GAUSSIAN_BLUR: sigma, finite, 0 < sigma <= 1e6 */
+  int32_t reserved[2]; /* must be 0; GAUSSIAN_BLUR: reserved[0] is the kernel size k (odd, 3..33), reserved[1] 0 */
 } mxd_enhance;
 
 /* Host only: the CPU statement of the arithmetic above on the w x h packed
@@ -773,6 +796,19 @@ int mxd_enhance_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, int64_t strid
 /* Host only: the checks the calls below make of one entry (MXD_OK, or
  * MXD_ERR_INVALID with their message). */
 int mxd_enhance_validate(const mxd_enhance* enh);
+/* Host only: the k weights of MXD_ENHANCE_GAUSSIAN_BLUR into out[0..k-1],
+ * torchvision's _get_gaussian_kernel1d computed in double: x_j = j - R,
+ * p_j = exp(-0.5 (x_j / sigma)^2) with sigma widened to double,
+ * w_j = (float)(p_j / sum p); a weight of magnitude under 2^-126 is stored as
+ * 0, so no float32 denormal reaches the device.  MXD_ERR_INVALID for a k that
+ * is even or outside 3..33, a sigma that is not finite, not > 0 or above 1e6,
+ * or a null out. */
+int mxd_gaussian_weights(float sigma, int32_t k, float* out);
+/* Measurements only (process-wide, like the tuning knobs): the shape of the
+ * blur kernel's work split -- output rows per workgroup segment (> 0) and
+ * source rows per step (4 or 8); 0 = the measured default.  The result bytes
+ * do not depend on it.  MXD_ERR_INVALID for anything else. */
+int mxd_blur_shape(int32_t seg_rows, int32_t step);
 
 /* The _warp calls with enhances[i] applied to images[i]'s result after
  * warps[i] and before tones[i].  warps, tones, colors and fmt may each be
@@ -781,7 +817,8 @@ int mxd_enhance_validate(const mxd_enhance* enh);
  * a negative, non-finite or too large factor, a non-zero reserved, or
  * channels != 3; everything is validated before any launch.  Every image is
  * resized as a u8 image into a scratch by the kernels of the plain calls; one
- * more launch on the same stream (enhance_rows) reads those rows, or the warp
+ * more launch on the same stream (enhance_rows; blur_rows for the images whose
+ * op is GAUSSIAN_BLUR) reads those rows, or the warp
  * stage's, and writes the destinations when nothing follows, else the other
  * of the two scratches, which the row stage of the _tone calls reads. */
 int mxd_resize_crop_batch_enhance(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,

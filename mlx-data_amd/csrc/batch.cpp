@@ -424,6 +424,13 @@ int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDe
   } else if (st.kind == StageKind::Enhance) {
     what = "enhance launch failed: ";
     rc = mxd::launch_enhance(static_cast<const mxd::EnhanceRowDev*>(entries), st.count, st.blocks, stream);
+    if (rc == 0 && L.blur_count > 0) {
+      what = "blur launch failed: ";
+      const int32_t step = g_blur_step.load();
+      rc = mxd::launch_blur(static_cast<const mxd::EnhanceRowDev*>(entries),
+                            reinterpret_cast<const mxd::BlurRecDev*>(dev + L.blur_at), L.blur_count, L.blur_units,
+                            step > 0 ? step : kBlurStep, stream);
+    }
   } else if (st.kind == StageKind::Mix) {
     what = "mix launch failed: ";
     rc = mxd::launch_mix(static_cast<const mxd::MixRowDev*>(entries), st.count, st.blocks, ofd, stream);

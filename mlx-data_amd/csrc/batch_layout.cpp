@@ -420,11 +420,47 @@ void fill_enhances(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
     mxd::EnhanceRowDev& e = L.enhance_entry(i);
     e.tile_begin = st.blocks;
     e.tiles_x = (im.crop_w + mxd::kEnhTileW - 1) / mxd::kEnhTileW;
-    st.blocks += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
+    // A blurred image is blur_rows' (append_blurs): no tile here.  enhance_rows
+    // takes the last entry with tile_begin <= its workgroup, so an entry
+    // without tiles -- it begins where the next one does, or at the launch's
+    // end -- is never chosen.
+    if (en.op != MXD_ENHANCE_GAUSSIAN_BLUR) st.blocks += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
     e.op = en.op;
     // (MXD_ENHANCE_NONE reads no factor: zero, so equal calls make equal bytes)
     e.factor = en.op == MXD_ENHANCE_NONE ? 0.0f : en.factor;
   }
+}
+
+// The blur table, behind every stage's entries and only when some image
+// blurs: one record per blurred image, in batch order.  k and the weights
+// (hence sigma) are part of the upload's bytes, so a cached slot is reused
+// only for the same ones.
+void append_blurs(Batch& b, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  std::vector<mxd::BlurRecDev> recs;
+  const int32_t knob = g_blur_seg_rows.load();
+  for (int32_t i = 0; i < b.n; i++) {
+    const mxd_enhance& en = ops.enhances[i];
+    if (en.op != MXD_ENHANCE_GAUSSIAN_BLUR) continue;
+    const mxd_image& im = L.images[i];
+    mxd::BlurRecDev r{};
+    r.entry = i;
+    r.unit_begin = L.blur_units;
+    r.strips = (im.crop_w + mxd::kBlurStripW - 1) / mxd::kBlurStripW;
+    r.seg_rows = knob > 0 ? knob : kBlurSegRows;
+    r.k = en.reserved[0];
+    float w[2 * mxd::kBlurMaxR + 1];
+    gaussian_weights(en.factor, r.k, w);
+    const int32_t R = (r.k - 1) / 2;
+    for (int32_t d = 0; d <= R; d++) r.w[d] = w[R + d];
+    L.blur_units += r.strips * ((im.crop_h + r.seg_rows - 1) / r.seg_rows);
+    recs.push_back(r);
+  }
+  if (recs.empty()) return;
+  L.blur_at = L.descs.size();
+  L.blur_count = (int32_t)recs.size();
+  L.descs.resize(L.blur_at + (recs.size() * sizeof(mxd::BlurRecDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+  std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.blur_at), recs.data(), recs.size() * sizeof(mxd::BlurRecDev));
 }
 
 // The mix stage's own fields: partners, ops, weights and boxes are part of the
@@ -533,6 +569,7 @@ void append_stages(Batch& b, const mxd_image* callers, const PostOps& ops) {
     if (kind == StageKind::Enhance) fill_enhances(b, *st, ops);
     if (kind == StageKind::Mix) fill_mixes(b, *st, ops);
   }
+  if (ops.enhances) append_blurs(b, ops);
 }
 
 }  // namespace

@@ -400,6 +400,10 @@ struct BatchLayout {
   int32_t warp_tiles() const { return warped() ? stage(StageKind::Warp)->blocks : 0; }
   int32_t warp_tab_count() const { return warped() ? stage(StageKind::Warp)->pre_blocks : 0; }
   int32_t enhance_tiles() const { return enhanced() ? stage(StageKind::Enhance)->blocks : 0; }
+  // The blur table (blur.hip): blur_count records from block blur_at, behind
+  // every stage's entries, for blur_units workgroups; none without a blurred image.
+  size_t blur_at = 0;
+  int32_t blur_count = 0, blur_units = 0;
   bool mixed() const { return stage(StageKind::Mix) != nullptr; }
   size_t mix_at() const { return mixed() ? stage(StageKind::Mix)->at : 0; }
   int32_t mix_blocks() const { return mixed() ? stage(StageKind::Mix)->blocks : 0; }
@@ -486,6 +490,12 @@ int warp_validate_one(const mxd_warp& warp, int32_t w, int32_t h);
 // Enhance operations (enhance.cpp).
 // enhances[i] against images[i] (images may be null: the entries alone).
 int enhance_validate(const mxd_image* images, const mxd_enhance* enhances, int32_t n);
+// mxd_gaussian_weights of a validated sigma and k.
+int gaussian_weights(float sigma, int32_t k, float* out);
+// blur_rows' shape: output rows per segment and source
+// rows per step, chosen by measurement; mxd_blur_shape overrides them.
+constexpr int32_t kBlurSegRows = 112, kBlurStep = 8;
+extern std::atomic<int32_t> g_blur_seg_rows, g_blur_step;
 
 // ---------------------------------------------------------------------------
 // MixUp / CutMix (mix.cpp).

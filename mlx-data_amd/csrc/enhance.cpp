@@ -1,21 +1,36 @@
 // enhance.cpp -- the per-image enhance operations (mxd_enhance,
 // capi_internal.h): the CPU statement of the arithmetic (mxd_enhance_apply_u8)
 // in plain C++, and the validation of the _enhance calls.  The arithmetic is
-// Pillow's ImageEnhance.Sharpness / Color / Brightness, bit for bit (DESIGN.md
-// section 2).  The device side is enhance.hip; the two share no code.
+// Pillow's ImageEnhance.Sharpness / Color / Brightness, bit for bit, and for
+// GAUSSIAN_BLUR a separable Gaussian with torchvision's kernel and reflect
+// padding.  The device side is enhance.hip and blur.hip;
+// the two sides share no code.
 // Host only.
 #include "capi_internal.h"
+
+#include <vector>
 
 #pragma clang fp contract(off)
 
 namespace mxd {
 namespace capi {
+
+std::atomic<int32_t> g_blur_seg_rows{0}, g_blur_step{0};
+
 namespace {
 
 int enhance_check(const mxd_enhance& e, int32_t i) {
   auto at = [i](const std::string& msg) {
     return fail(MXD_ERR_INVALID, "mxd_enhance: " + msg + " (image " + std::to_string(i) + ")");
   };
+  if (e.op == MXD_ENHANCE_GAUSSIAN_BLUR) {
+    if (e.reserved[1] != 0) return at("reserved[1] must be 0");
+    if (e.reserved[0] < 3 || e.reserved[0] > 33 || e.reserved[0] % 2 == 0)
+      return at("reserved[0] (the kernel size) must be odd and in 3..33");
+    if (!(std::isfinite(e.factor) && e.factor > 0.0f && e.factor <= 1e6f))
+      return at("factor (sigma) must be finite, > 0 and at most 1e6");
+    return MXD_OK;
+  }
   if (e.op < MXD_ENHANCE_NONE || e.op > MXD_ENHANCE_BRIGHTNESS) return at("unknown op " + std::to_string(e.op));
   if (e.reserved[0] != 0 || e.reserved[1] != 0) return at("reserved must be 0");
   if (e.op != MXD_ENHANCE_NONE && !(std::isfinite(e.factor) && e.factor >= 0.0f && e.factor <= 1e6f))
@@ -35,7 +50,66 @@ inline uint8_t blend(int d, int q, float f) {
   return y <= 0.0f ? 0 : y >= 255.0f ? 255 : (uint8_t)(int)y;
 }
 
+// torch / NumPy "reflect" of index i into 0..n-1: the mirror without the edge
+// repeated, period 2 (n - 1).
+inline int reflect(int i, int n) {
+  if (n == 1) return 0;
+  const int p = 2 * (n - 1);
+  i %= p;
+  if (i < 0) i += p;
+  return i < n ? i : p - i;
+}
+
+// GAUSSIAN_BLUR (mxd_amd.h): the H pass of every row into float32, then the V
+// pass, each operation rounded on its own.
+void gaussian_blur(const uint8_t* rgb, int w, int h, int64_t stride, const float* wt, int R, uint8_t* out,
+                   int64_t out_stride) {
+  const int n = w * 3;
+  std::vector<float> hp((size_t)h * n);
+  std::vector<int> xl(w * (R + 1)), xr(w * (R + 1));
+  for (int x = 0; x < w; x++)
+    for (int d = 0; d <= R; d++) xl[x * (R + 1) + d] = reflect(x - d, w), xr[x * (R + 1) + d] = reflect(x + d, w);
+  for (int y = 0; y < h; y++) {
+    const uint8_t* q = rgb + (int64_t)y * stride;
+    for (int x = 0; x < w; x++)
+      for (int c = 0; c < 3; c++) {
+        volatile float a = wt[R] * (float)q[3 * x + c];
+        for (int d = 1; d <= R; d++) {
+          volatile float t = wt[R + d] * (float)((int)q[3 * xl[x * (R + 1) + d] + c] + (int)q[3 * xr[x * (R + 1) + d] + c]);
+          a = a + t;
+        }
+        hp[(size_t)y * n + 3 * x + c] = a;
+      }
+  }
+  for (int y = 0; y < h; y++)
+    for (int i = 0; i < n; i++) {
+      volatile float a = wt[R] * hp[(size_t)y * n + i];
+      for (int d = 1; d <= R; d++) {
+        volatile float s = hp[(size_t)reflect(y - d, h) * n + i] + hp[(size_t)reflect(y + d, h) * n + i];
+        volatile float t = wt[R + d] * s;
+        a = a + t;
+      }
+      const float r = std::nearbyint((float)a);  // half to even in the default rounding mode
+      out[(int64_t)y * out_stride + i] = (uint8_t)(r <= 0.0f ? 0.0f : r >= 255.0f ? 255.0f : r);
+    }
+}
+
 }  // namespace
+
+int gaussian_weights(float sigma, int32_t k, float* out) {
+  const int R = (k - 1) / 2;
+  double p[33], sum = 0.0;
+  for (int j = 0; j < k; j++) {
+    const double x = (double)(j - R) / (double)sigma;
+    p[j] = std::exp(-0.5 * (x * x));
+    sum += p[j];
+  }
+  for (int j = 0; j < k; j++) {
+    const float w = (float)(p[j] / sum);
+    out[j] = std::fabs(w) < 0x1p-126f ? 0.0f : w;
+  }
+  return MXD_OK;
+}
 
 int enhance_validate(const mxd_image* images, const mxd_enhance* enhances, int32_t n) {
   if (n > 0 && !enhances) return fail(MXD_ERR_INVALID, "mxd: null enhances");
@@ -54,6 +128,20 @@ using namespace mxd::capi;
 
 extern "C" int mxd_enhance_validate(const mxd_enhance* enh) { return enhance_validate(nullptr, enh, 1); }
 
+extern "C" int mxd_blur_shape(int32_t seg_rows, int32_t step) {
+  if (seg_rows < 0 || (step != 0 && step != 4 && step != 8)) return fail(MXD_ERR_INVALID, "mxd_blur_shape: bad shape");
+  g_blur_seg_rows = seg_rows;
+  g_blur_step = step;
+  return MXD_OK;
+}
+
+extern "C" int mxd_gaussian_weights(float sigma, int32_t k, float* out) {
+  const mxd_enhance e{MXD_ENHANCE_GAUSSIAN_BLUR, sigma, {k, 0}};
+  if (int rc = mxd_enhance_validate(&e)) return rc;
+  if (!out) return fail(MXD_ERR_INVALID, "mxd: null weights");
+  return gaussian_weights(sigma, k, out);
+}
+
 extern "C" int mxd_enhance_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, int64_t stride, const mxd_enhance* enh,
                                     uint8_t* out, int64_t out_stride) {
   if (int rc = mxd_enhance_validate(enh)) return rc;
@@ -68,6 +156,12 @@ extern "C" int mxd_enhance_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, in
   auto dst = [&](int y, int x) { return out + (int64_t)y * out_stride + (int64_t)x * 3; };
   const int op = enh->op;
   const float f = enh->factor;
+  if (op == MXD_ENHANCE_GAUSSIAN_BLUR) {
+    float wt[33];
+    gaussian_weights(f, enh->reserved[0], wt);
+    gaussian_blur(rgb, w, h, stride, wt, (enh->reserved[0] - 1) / 2, out, out_stride);
+    return MXD_OK;
+  }
   for (int y = 0; y < h; y++)
     for (int x = 0; x < w; x++) {
       const uint8_t* q = src(y, x);

@@ -337,7 +337,7 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
     }
     m.warped = m.warped || j.plan.warped;
     mxd_enhance e{};  // (MXD_ENHANCE_NONE for a plan without an enhance op)
-    if (j.plan.enhanced) e.op = j.plan.enhance_op, e.factor = j.plan.enhance_factor;
+    if (j.plan.enhanced) e.op = j.plan.enhance_op, e.factor = j.plan.enhance_factor, e.reserved[0] = j.plan.enhance_ksize;
     m.enhanced = m.enhanced || j.plan.enhanced;
     if (auto src = j.plan.src->jpeg()) {
       jp.add(jpeg_desc(j.plan, *src, j.dst, j.stride), c, t, w, e);
@@ -810,8 +810,8 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
     return out;
   }
   ImagePlan p = geometry_view(img);
-  if ((p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) || (p.enhanced && p.enhance_op == MXD_ENHANCE_SHARPNESS)) {
-    // the op's statistics (SHARPNESS: copied ring) are those of the window it saw: run it, crop its bytes
+  if ((p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) || (p.enhanced && (p.enhance_op == MXD_ENHANCE_SHARPNESS || p.enhance_op == MXD_ENHANCE_GAUSSIAN_BLUR))) {
+    // the op's statistics (SHARPNESS: copied ring; GAUSSIAN_BLUR: reflected edges) are those of the window it saw: run it, crop its bytes
     img->data();
     p = view(img);
   }
@@ -1253,6 +1253,7 @@ std::shared_ptr<Array> ImageAffine::apply_video(const std::shared_ptr<Array>& vi
 // ---- enhance ops: mark the plan ------------------------------------------------
 const char* enhance_name(int32_t op) {
   static const char* const names[] = {"none", "sharpness", "color", "brightness"};
+  if (op == MXD_ENHANCE_GAUSSIAN_BLUR) return "gaussian_blur";
   return op >= 0 && op <= MXD_ENHANCE_BRIGHTNESS ? names[op] : "none";
 }
 
@@ -1262,16 +1263,31 @@ namespace {
 bool enhance_factor_ok(double f) { return std::isfinite(f) && f >= 0.0 && f <= 1e6; }
 }  // namespace
 
-ImageEnhance::ImageEnhance(std::string ikey, int32_t op, double factor, std::string okey)
-    : ImageOp(std::move(ikey), std::move(okey)), op_(op), random_(false), lo_(factor), hi_(factor) {
-  if (!enhance_factor_ok(factor)) throw std::invalid_argument(name() + ": factor must be finite and in 0..1e6");
+// A blur's sigma is checked as the float32 the launch takes.
+void ImageEnhance::check_args(const char* what) const {
+  if (op_ != MXD_ENHANCE_GAUSSIAN_BLUR) {
+    if (!enhance_factor_ok(lo_) || !enhance_factor_ok(hi_))
+      throw std::invalid_argument(name() + ": factor" + what + " must be finite and in 0..1e6");
+    return;
+  }
+  if (ksize_ < 3 || ksize_ > 33 || ksize_ % 2 == 0)
+    throw std::invalid_argument(name() + ": kernel_size must be odd and in 3..33");
+  for (double s : {lo_, hi_})
+    if (!(std::isfinite(s) && (float)s > 0.0f && s <= 1e6))
+      throw std::invalid_argument(name() + ": sigma" + what + " must be finite, > 0 and at most 1e6");
 }
 
-ImageEnhance::ImageEnhance(std::string ikey, int32_t op, std::pair<double, double> range, std::string okey)
-    : ImageOp(std::move(ikey), std::move(okey)), op_(op), random_(true), lo_(range.first), hi_(range.second) {
-  if (!enhance_factor_ok(lo_) || !enhance_factor_ok(hi_))
-    throw std::invalid_argument(name() + ": factor range must be finite and in 0..1e6");
-  if (lo_ > hi_) throw std::invalid_argument(name() + ": factor range has lo > hi");
+ImageEnhance::ImageEnhance(std::string ikey, int32_t op, double factor, std::string okey, int32_t ksize)
+    : ImageOp(std::move(ikey), std::move(okey)), op_(op), random_(false), lo_(factor), hi_(factor), ksize_(ksize) {
+  check_args("");
+}
+
+ImageEnhance::ImageEnhance(std::string ikey, int32_t op, std::pair<double, double> range, std::string okey, int32_t ksize)
+    : ImageOp(std::move(ikey), std::move(okey)), op_(op), random_(true), lo_(range.first), hi_(range.second),
+      ksize_(ksize) {
+  check_args(" range");
+  if (lo_ > hi_)
+    throw std::invalid_argument(name() + (op_ == MXD_ENHANCE_GAUSSIAN_BLUR ? ": sigma" : ": factor") + " range has lo > hi");
 }
 
 double ImageEnhance::factor() const {
@@ -1292,6 +1308,7 @@ std::shared_ptr<Array> ImageEnhance::mark(const std::shared_ptr<Array>& img, dou
   p.enhanced = true;
   p.enhance_op = op_;
   p.enhance_factor = (float)factor;
+  p.enhance_ksize = ksize_;
   return make(p);
 }
 

@@ -129,10 +129,14 @@ struct ImagePlan {
   // are pointwise, and SMOOTH is symmetric); a crop after SHARPNESS, whose
   // copied ring is the uncropped window's, a resize, image_rotate, a warp op
   // or a second enhance op materialises the plan first, as an enhance op on a
-  // plan already toned or coloured does.
+  // plan already toned or coloured does.  image_gaussian_blur and its random
+  // form are MXD_ENHANCE_GAUSSIAN_BLUR (enhance_factor: sigma; enhance_ksize:
+  // the kernel size) with SHARPNESS's rules: the symmetric form of the blur
+  // makes the flip compose, and its reflected edges are the uncropped window's.
   bool enhanced = false;
   int32_t enhance_op = 0;
   float enhance_factor = 1.0f;
+  int32_t enhance_ksize = 0;  // GAUSSIAN_BLUR only
   int64_t channels() const;
 };
 
@@ -461,13 +465,16 @@ std::array<double, 6> affine_rotate_matrix(int64_t w, int64_t h, double angle);
 // op only marks the pending plan.  RGB images only: "image_sharpness: image
 // must have 3 channels, not N" otherwise.  Bad arguments throw
 // std::invalid_argument from the constructors.
+// MXD_ENHANCE_GAUSSIAN_BLUR (image_gaussian_blur) is torchvision's
+// GaussianBlur: factor is sigma (finite, > 0 as a float32, <= 1e6) and ksize
+// the kernel size (odd, 3..33); every other op takes ksize 0.
 class ImageEnhance : public ImageOp {
  public:
   // op: mxd_enhance_op (not NONE); factor: finite, 0 <= factor <= 1e6.
-  ImageEnhance(std::string ikey, int32_t op, double factor, std::string okey);
+  ImageEnhance(std::string ikey, int32_t op, double factor, std::string okey, int32_t ksize = 0);
   // The random forms: one uniform double in [lo, hi] from the thread's
   // generator per image; a video draws once for all its frames.
-  ImageEnhance(std::string ikey, int32_t op, std::pair<double, double> range, std::string okey);
+  ImageEnhance(std::string ikey, int32_t op, std::pair<double, double> range, std::string okey, int32_t ksize = 0);
   std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
   std::shared_ptr<Array> apply_video(const std::shared_ptr<Array>& video) const override;
 
@@ -475,11 +482,13 @@ class ImageEnhance : public ImageOp {
   std::string name() const;
   double factor() const;  // the fixed one, or a draw
   std::shared_ptr<Array> mark(const std::shared_ptr<Array>& img, double factor) const;
+  void check_args(const char* what) const;
   int32_t op_;
   bool random_;
   double lo_, hi_;
+  int32_t ksize_;
 };
-// "sharpness", "color", "brightness" of an mxd_enhance_op (the op is image_<name>).
+// "sharpness", "color", "brightness", "gaussian_blur" of an mxd_enhance_op (the op is image_<name>).
 const char* enhance_name(int32_t op);
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the

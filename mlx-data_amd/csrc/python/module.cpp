@@ -622,6 +622,25 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
           },
           py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
       .def(
+          "image_gaussian_blur",
+          [wrap](const Self& self, const std::string& key, int32_t kernel_size, double sigma, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_GAUSSIAN_BLUR, sigma, output_key, kernel_size));
+          },
+          py::arg("key"), py::arg("kernel_size"), py::arg("sigma"), py::arg("output_key") = "")
+      .def(
+          "image_random_gaussian_blur",
+          [wrap](const Self& self, const std::string& key, int32_t kernel_size, const py::object& sigma,
+                 const std::string& output_key) {
+            std::pair<double, double> range;
+            try {
+              range = sigma.cast<std::pair<double, double>>();
+            } catch (const py::cast_error&) {
+              throw std::invalid_argument("image_random_gaussian_blur: sigma must be a (lo, hi) pair");
+            }
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_GAUSSIAN_BLUR, range, output_key, kernel_size));
+          },
+          py::arg("key"), py::arg("kernel_size"), py::arg("sigma") = py::make_tuple(0.1, 2.0), py::arg("output_key") = "")
+      .def(
           "image_color",
           [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
             return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_COLOR, factor, output_key));
@@ -962,8 +981,10 @@ PYBIND11_MODULE(_pipeline, m) {
     } else {
       d["warp"] = py::none();
     }
-    // the enhance op: (name, factor)
-    if (p.enhanced) d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor));
+    // the enhance op: (name, factor); a blur: ("gaussian_blur", sigma, kernel size)
+    if (p.enhanced && p.enhance_op == MXD_ENHANCE_GAUSSIAN_BLUR)
+      d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor), p.enhance_ksize);
+    else if (p.enhanced) d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor));
     else d["enhance"] = py::none();
     return d;
   });

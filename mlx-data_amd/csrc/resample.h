@@ -267,7 +267,7 @@ int launch_warp(const WarpRowDev* rows, int nimgs, int ntiles, int tab_rows, uin
 // stage cannot run in place: src and dst are different rows.
 constexpr int kEnhTileW = 64, kEnhTileH = 16;
 // mxd_enhance_op's values.
-enum EnhanceOp : int32_t { kEnhNone = 0, kEnhSharpness = 1, kEnhColor = 2, kEnhBrightness = 3 };
+enum EnhanceOp : int32_t { kEnhNone = 0, kEnhSharpness = 1, kEnhColor = 2, kEnhBrightness = 3, kEnhGaussianBlur = 8 };
 struct EnhanceRowDev {
   const uint8_t* src;  // u8 rows (16-byte aligned base, stride a multiple of 16)
   uint8_t* dst;        // scratch rows like src, or the caller's u8 destination (any alignment)
@@ -280,6 +280,27 @@ struct EnhanceRowDev {
 };
 static_assert(sizeof(EnhanceRowDev) == 56, "EnhanceRowDev layout");
 int launch_enhance(const EnhanceRowDev* rows, int nimgs, int ntiles, void* stream);
+// The Gaussian blur of the enhance stage (blur.hip): an image whose op is
+// kEnhGaussianBlur has no tile in enhance_rows (its entry is skipped by the
+// tile_begin lookup, which takes the last entry that begins at or before a
+// workgroup) and one record in a table of its own behind every stage's entries.
+// blur_rows takes a strip of kBlurStripW output pixels times a segment of
+// seg_rows output rows per workgroup, units numbered through unit_begin; it
+// reads the image's rows from its enhance entry.  The weights are part of the
+// uploaded bytes, so a cached descriptor slot serves the same sigma and k only.
+constexpr int kBlurStripW = 64, kBlurMaxR = 16;
+struct BlurRecDev {
+  int32_t entry;       // the image's entry among the enhance stage's
+  int32_t unit_begin;  // first of the image's workgroups among the launch's
+  int32_t strips;      // strips per row of segments
+  int32_t seg_rows;    // output rows per segment
+  int32_t k;           // kernel size, R = (k - 1) / 2
+  int32_t pad[2];
+  float w[kBlurMaxR + 1];  // w[d]: the weight at distance d from the centre (0 beyond R)
+};
+static_assert(sizeof(BlurRecDev) == 96, "BlurRecDev layout");
+// step: source rows per step of the walk, 4 or 8.
+int launch_blur(const EnhanceRowDev* rows, const BlurRecDev* recs, int nrecs, int nunits, int step, void* stream);
 // The mix stage (mix.hip): the last stage of a mix call (mxd_mix), over u8 RGB
 // scratch rows.  One entry per image; a workgroup takes kMixRows rows of one
 // image, workgroups numbered through blk_begin.  It reads the image's rows

@@ -48,7 +48,8 @@ EXPORTS = (
     "mxd_resize_crop_to_device_tone", "mxd_jpeg_resize_crop_to_device_tone",
     "mxd_warp_validate", "mxd_warp_apply_u8", "mxd_resize_crop_batch_warp", "mxd_resize_crop_to_device_warp",
     "mxd_jpeg_resize_crop_to_device_warp",
-    "mxd_enhance_validate", "mxd_enhance_apply_u8", "mxd_resize_crop_batch_enhance",
+    "mxd_enhance_validate", "mxd_enhance_apply_u8", "mxd_gaussian_weights", "mxd_blur_shape",
+    "mxd_resize_crop_batch_enhance",
     "mxd_resize_crop_to_device_enhance", "mxd_jpeg_resize_crop_to_device_enhance",
     "mxd_mix_validate", "mxd_mix_apply_u8", "mxd_resize_crop_batch_mix", "mxd_resize_crop_to_device_mix",
     "mxd_jpeg_resize_crop_to_device_mix",
@@ -471,6 +472,7 @@ MXD_ENHANCE_NONE = 0
 MXD_ENHANCE_SHARPNESS = 1
 MXD_ENHANCE_COLOR = 2
 MXD_ENHANCE_BRIGHTNESS = 3
+MXD_ENHANCE_GAUSSIAN_BLUR = 8  # factor: sigma; a third tuple member: the kernel size
 
 
 class MxdEnhance(ctypes.Structure):
@@ -480,7 +482,8 @@ class MxdEnhance(ctypes.Structure):
 
 
 def make_enhances(enhances):
-    """(op, factor) tuples (or MxdEnhance values) -> ctypes array of mxd_enhance."""
+    """(op, factor) tuples -- (MXD_ENHANCE_GAUSSIAN_BLUR, sigma, kernel_size) for a blur --
+    (or MxdEnhance values) -> ctypes array of mxd_enhance."""
     arr = (MxdEnhance * max(1, len(enhances)))()
     for i, e in enumerate(enhances):
         if isinstance(e, MxdEnhance):
@@ -488,7 +491,22 @@ def make_enhances(enhances):
             continue
         arr[i].op = int(e[0])
         arr[i].factor = float(e[1])
+        if len(e) > 2:
+            arr[i].reserved[0] = int(e[2])
     return arr
+
+
+def gaussian_weights(sigma, kernel_size):
+    """mxd_gaussian_weights: the kernel_size float32 weights of MXD_ENHANCE_GAUSSIAN_BLUR."""
+    out = np.zeros(max(1, int(kernel_size)), np.float32)
+    check(lib().mxd_gaussian_weights(ctypes.c_float(sigma), int(kernel_size), ctypes.c_void_p(out.ctypes.data)))
+    return out[:int(kernel_size)]
+
+
+def blur_shape(seg_rows=0, step=0):
+    """mxd_blur_shape (measurements): output rows per segment and source rows per step
+    (4 or 8) of the blur kernel; 0 = the default."""
+    check(lib().mxd_blur_shape(int(seg_rows), int(step)))
 
 
 def enhance_validate(enhance):

@@ -140,6 +140,17 @@ warp or a second enhance op, or an enhance op after a tone or colour op,
 materialises what is pending.  Bad arguments raise ``ValueError`` when the op
 is made.
 
+``image_gaussian_blur(key, kernel_size, sigma)`` and
+``image_random_gaussian_blur(key, kernel_size, sigma=(lo, hi))`` are the blur
+of the self-supervised recipes (torchvision's ``GaussianBlur``: its kernel,
+``reflect`` padding, a true separable Gaussian -- not Pillow's box-blur
+approximation) as one more enhance op of the same launch: ``kernel_size`` is
+odd and in 3..33, ``sigma`` finite, > 0 and at most 1e6, the random form draws
+one uniform sigma per image (a video draws once).  The arithmetic is fixed bit
+for bit (``include/mxd_amd.h``).  It composes as ``image_sharpness`` does: a
+flip, tone and colour ops and the output forms after it; a crop, resize,
+``image_rotate``, warp or second enhance op materialises what is pending.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole
@@ -214,7 +225,8 @@ def _add_if_variants(cls):
                  "image_affine", "image_shear", "image_translate", "image_affine_rotate", "image_random_shear",
                  "image_random_translate", "image_random_affine_rotate",
                  "image_sharpness", "image_color", "image_brightness", "image_random_sharpness",
-                 "image_random_color", "image_random_brightness"):
+                 "image_random_color", "image_random_brightness", "image_gaussian_blur",
+                 "image_random_gaussian_blur"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 

@@ -20,6 +20,17 @@ process for --rounds rounds (3 rounds: 9 windows each):
           copy, the blend, truncate, clamp, / 255, normalise, permute and cast
           to bfloat16
 
+--op blur times the Gaussian blur in the same A/B shape:
+
+  b       mxd_resize_crop_batch_enhance, MXD_ENHANCE_GAUSSIAN_BLUR with k = 23
+          and sigma 2.0 for every image (blur_rows), the same format
+  bS_T    as b with S output rows per segment and T source rows per step
+          (mxd_blur_shape), one variant per entry of --blur-shapes S:T,...
+  d       the u8 mxd_resize_crop_batch, then torch on the same stream: reflect
+          pad, depthwise conv2d with the outer product of the same weights,
+          round, clamp, / 255, normalise, permute and cast to bfloat16
+  a, a2, n as above; c is not run
+
 --variants picks a subset (a profiler run of the enhance call alone: --variants b).
 --lib times another build of the library: enhance.hip compiled with
 -DMXD_ENH_LDS stages the tile and its halo in LDS instead of reading the
@@ -45,7 +56,10 @@ STD = (0.229, 0.224, 0.225)
 FACTOR = 1.5
 
 
-def run_workload(name, capi, torch, rounds, emit, only):
+BLUR_K, BLUR_SIGMA = 23, 2.0
+
+
+def run_workload(name, capi, torch, rounds, emit, only, op="sharpness", blur_shapes=()):
     import torch.nn.functional as F
 
     dev = 0
@@ -101,6 +115,29 @@ def run_workload(name, capi, torch, rounds, emit, only):
             ((y / 255 - mean_t) / std_t).to(torch.bfloat16)
 
     every = {"a": a, "b": enhance_call(sharp), "c": enhance_call(color), "n": enhance_call(none), "d": d, "a2": a}
+    if op == "blur":
+        blur = capi.make_enhances([(capi.MXD_ENHANCE_GAUSSIAN_BLUR, BLUR_SIGMA, BLUR_K)] * B)
+        w1 = torch.from_numpy(capi.gaussian_weights(BLUR_SIGMA, BLUR_K).copy()).to("cuda:0")
+        w2 = torch.outer(w1, w1).view(1, 1, BLUR_K, BLUR_K).expand(C, 1, BLUR_K, BLUR_K).contiguous()
+
+        def shaped(seg, step):
+            f = enhance_call(blur)
+
+            def g(i):
+                capi.blur_shape(seg, step)
+                f(i)
+                capi.blur_shape(0, 0)
+            return g
+
+        def d_blur(i):
+            call(L.mxd_resize_crop_batch(arrays["u8"][i % 2], B, capi.MXD_U8, dev, hs))
+            with torch.cuda.stream(ext):
+                x = F.pad(u8s[i % 2].permute(0, 3, 1, 2).float(), (BLUR_K // 2,) * 4, mode="reflect")
+                y = torch.clamp(torch.round(F.conv2d(x, w2, groups=C)), 0, 255)
+                ((y / 255 - mean_t) / std_t).to(torch.bfloat16)
+
+        every = {"a": a, "b": enhance_call(blur), "n": enhance_call(none), "d": d_blur, "a2": a}
+        every.update({f"b{seg}_{step}": shaped(seg, step) for seg, step in blur_shapes})
     variants = {k: f for k, f in every.items() if not only or k in only}
     try:
         for f in variants.values():  # every shape and variant warmed first
@@ -116,7 +153,13 @@ def run_workload(name, capi, torch, rounds, emit, only):
             med[k] = statistics.median(w)
             emit({"workload": name, "variant": k, "images": B, "ms_per_launch": round(med[k], 5), "min": min(w),
                   "max": max(w), "windows": w})
-        if not only:
+        if not only and op == "blur":
+            lo = min(med["a"], med["a2"])
+            emit({"workload": name, "summary": True, "op": "gaussian_blur", "k": BLUR_K, "sigma": BLUR_SIGMA,
+                  "b_over_a": round(med["b"] / lo, 4), "n_over_a": round(med["n"] / lo, 4),
+                  "d_over_b": round(med["d"] / med["b"], 2), "a_spread": round(abs(med["a"] - med["a2"]) / lo, 4),
+                  "shapes_over_a": {k: round(m / lo, 4) for k, m in med.items() if k.startswith("b") and k != "b"}})
+        elif not only:
             lo = min(med["a"], med["a2"])
             emit({"workload": name, "summary": True, "b_over_a": round(med["b"] / lo, 4), "c_over_a": round(med["c"] / lo, 4),
                   "n_over_a": round(med["n"] / lo, 4), "d_over_b": round(med["d"] / med["b"], 2),
@@ -135,6 +178,8 @@ def main():
     ap.add_argument("--workloads", default="c2,c4")
     ap.add_argument("--variants", default="")
     ap.add_argument("--out", default="")
+    ap.add_argument("--op", default="sharpness", choices=("sharpness", "blur"))
+    ap.add_argument("--blur-shapes", default="", help="--op blur: segment rows : rows per step, e.g. 32:8,112:8,56:4")
     ap.add_argument("--lib", default="", help="another build of libmxd_amd.so to time (a compile-time variant)")
     args = ap.parse_args()
     import torch  # torch first: its HIP runtime is the one the libraries bind
@@ -160,7 +205,8 @@ def main():
           "method": "bench.launch_windows: device events, windows >= 100 launches and >= 20 ms, 3 per round"})
     only = set(args.variants.split(",")) if args.variants else set()
     for wl in args.workloads.split(","):
-        run_workload(wl, capi, torch, args.rounds, emit, only)
+        shapes = [tuple(int(v) for v in s.split(":")) for s in args.blur_shapes.split(",") if s]
+        run_workload(wl, capi, torch, args.rounds, emit, only, args.op, shapes)
 
 
 if __name__ == "__main__":
