@@ -77,7 +77,12 @@ extern "C" {
  * mxd_mix_validate, mxd_mix_apply_u8, mxd_resize_crop_batch_mix,
  * mxd_resize_crop_to_device_mix, mxd_jpeg_resize_crop_to_device_mix.
  * 7, added without a new number (test for MXD_HAS_GAUSSIAN_BLUR / the
- * symbols): the enhance op MXD_ENHANCE_GAUSSIAN_BLUR and mxd_gaussian_weights. */
+ * symbols): the enhance op MXD_ENHANCE_GAUSSIAN_BLUR and mxd_gaussian_weights.
+ * 7, added without a new number (test for MXD_HAS_ERASE / the symbols): Random
+ * Erasing behind the output form -- mxd_erase_mode, mxd_erase_elem, mxd_erase,
+ * mxd_erase_validate, mxd_erase_apply, mxd_erase_normals,
+ * mxd_resize_crop_batch_erase, mxd_resize_crop_to_device_erase,
+ * mxd_jpeg_resize_crop_to_device_erase. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
@@ -86,6 +91,7 @@ extern "C" {
 #define MXD_HAS_ENHANCE 1
 #define MXD_HAS_MIX 1
 #define MXD_HAS_GAUSSIAN_BLUR 1
+#define MXD_HAS_ERASE 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -906,6 +912,86 @@ int mxd_jpeg_resize_crop_to_device_mix(const mxd_jpeg_image* images, const mxd_w
                                        const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
                                        const mxd_mix* mixes, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
                                        int32_t device);
+
+/* ---- Random Erasing behind the output form (ABI 7 additions; feature test:
+ * MXD_HAS_ERASE)
+ *
+ * An erase acts on the output elements of one image -- float32, float16,
+ * bfloat16 or u8, HWC or CHW -- after everything else: the stage order of a
+ * call is geometry, warp, enhance, tone, colour, mix, output form, erase.  It
+ * is timm's RandomErasing (--reprob / --remode) and torchvision's, which act on
+ * the normalised batch.  An image has up to MXD_ERASE_MAX_BOXES boxes x0, y0,
+ * x1, y1 in the crop window's coordinates.  Element (c, y, x) with x0 <= x < x1
+ * and y0 <= y < y1 of a box gets the box's fill in the call's element type;
+ * where boxes overlap, the highest-numbered box that contains the element wins
+ * (timm applies them in order).  Elements outside every box are not written:
+ * they are the bytes the same call without erases writes.
+ *
+ *   CONST  value[c], cast to the element type (round to nearest even for the
+ *          16-bit types; for u8 an integer in 0..255).
+ *   COLOR  one standard normal per box and channel (timm's 'rand').
+ *   PIXEL  one standard normal per element (timm's 'pixel').
+ *   COLOR and PIXEL need a float element type.
+ *
+ * The noise is a pure function of (seed, box number b, c, y, x), whatever the
+ * layout, the element type and the launch: Philox4x32-10 with key = seed[0],
+ * seed[1].  PIXEL: counter (x >> 2, y, c, b); the four normals of the call go
+ * to x & 3 = 0..3.  COLOR: counter (0, 0, 0, 0x100 + b), normal c of the four.
+ * From the words w0..w3: u(w) = ((w >> 9) + 0.5) * 2^-23 (exact in float32,
+ * never 0 or 1); (z0, z1) = sqrt(-2 ln u(w0)) * (cos, sin)(2 pi u(w1)), and
+ * (z2, z3) likewise from w2, w3.  ln and sincos are written out in float32
+ * add, multiply, divide and sqrt (csrc/erase_noise.h), which the kernel and
+ * mxd_erase_apply share: both give the same bits.  Against a float64
+ * Box-Muller of the same words |z - z64| <= 2^-18 max(1, |z64|). */
+enum mxd_erase_mode { MXD_ERASE_CONST = 0, MXD_ERASE_COLOR = 1, MXD_ERASE_PIXEL = 2 };
+/* The element type an erase writes: u8, or mxd_elem + 1. */
+enum mxd_erase_elem { MXD_ERASE_U8 = 0, MXD_ERASE_F32 = 1, MXD_ERASE_F16 = 2, MXD_ERASE_BF16 = 3 };
+#define MXD_ERASE_MAX_BOXES 4
+
+typedef struct mxd_erase {
+  int32_t count;      /* boxes, 0..MXD_ERASE_MAX_BOXES; 0: not erased, only reserved is read */
+  int32_t mode;       /* mxd_erase_mode */
+  uint32_t seed[2];   /* COLOR, PIXEL: the Philox key */
+  float value[4];     /* CONST: value[c], finite */
+  int32_t box[MXD_ERASE_MAX_BOXES][4]; /* x0, y0, x1, y1; 0 <= x0 <= x1 <= crop_w, 0 <= y0 <= y1 <= crop_h */
+  int32_t reserved[8]; /* must be 0 */
+} mxd_erase;
+
+/* Host only: the checks the calls below make of erases[0..n) against
+ * images[0..n) for a call whose elements are `elem` (mxd_erase_elem).  images
+ * may be NULL: the entries alone (the boxes' upper bounds are not checked). */
+int mxd_erase_validate(const mxd_image* images, const mxd_erase* erases, int32_t n, int32_t elem);
+/* Host only: the CPU statement of the rule above on one w x h RGB image of
+ * `elem` elements in host memory: HWC (layout = MXD_LAYOUT_HWC: rows dst_stride
+ * bytes apart) or CHW (planes plane_stride bytes apart).  Only the elements
+ * inside the boxes are written. */
+int mxd_erase_apply(void* dst, int64_t dst_stride, int64_t plane_stride, int32_t w, int32_t h, int32_t elem,
+                    int32_t layout, const mxd_erase* erase);
+/* Host only: the four float32 normals of the Philox call with this counter and
+ * key, and (words != NULL) its four words. */
+int mxd_erase_normals(const uint32_t counter[4], const uint32_t key[2], float out[4], uint32_t* words);
+
+/* The _mix calls with erases[i] applied to images[i]'s output elements last.
+ * warps, enhances, tones, colors, mixes and fmt may each be NULL; erases may
+ * not.  Device destinations only, RGB only.  MXD_ERR_INVALID (the message names
+ * the image and the field) for a null erases, a count outside 0..4, an unknown
+ * mode, a bad box, a non-finite value (for u8: not an integer in 0..255), COLOR
+ * or PIXEL on u8 elements, channels != 3, or a non-zero reserved; everything is
+ * validated before any launch.  The call plans, uploads and launches what it
+ * does without erases; one more launch on the same stream (erase_boxes) then
+ * writes the boxes, with work proportional to the erased area. */
+int mxd_resize_crop_batch_erase(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                const mxd_tone* tones, const mxd_color* colors, const mxd_mix* mixes,
+                                const mxd_erase* erases, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                                int32_t device, void* stream);
+int mxd_resize_crop_to_device_erase(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,
+                                    const mxd_tone* tones, const mxd_color* colors, const mxd_mix* mixes,
+                                    const mxd_erase* erases, int32_t n, int32_t out_dtype, const mxd_out_format* fmt,
+                                    int32_t device);
+int mxd_jpeg_resize_crop_to_device_erase(const mxd_jpeg_image* images, const mxd_warp* warps,
+                                         const mxd_enhance* enhances, const mxd_tone* tones, const mxd_color* colors,
+                                         const mxd_mix* mixes, const mxd_erase* erases, int32_t n, int32_t out_dtype,
+                                         const mxd_out_format* fmt, int32_t device);
 
 /* Diagnostics: where a host-side pipeline's time goes, summed over every
  * thread since the last reset (reset != 0 zeroes them after reading).

@@ -471,6 +471,12 @@ int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_
   // The chain, behind the joins: every resize kernel that wrote scratch rows
   // is ordered before it on the caller's stream.
   for (int32_t s = 0; s < L.nstages && launch_rc == MXD_OK; s++) launch_rc = launch_stage(L, L.chain[s], dev, ofd, stream);
+  // The erase launch, behind whatever wrote the destinations: the chain's last
+  // stage, or the resize kernels themselves, joined above.
+  if (launch_rc == MXD_OK && L.erase_count > 0 &&
+      mxd::launch_erase(reinterpret_cast<const mxd::EraseRecDev*>(dev + L.erase_at), L.erase_count, L.erase_units,
+                        L.erase_elem, L.erase_chw, stream))
+    launch_rc = fail(MXD_ERR_DEVICE, std::string("erase launch failed: ") + hipGetErrorString(hipGetLastError()));
   // The batch is counted on a failed launch too (see launch_all).
   const int rel = release_descs(ws, stream, hit);
   return launch_rc != MXD_OK ? launch_rc : rel;
@@ -479,8 +485,14 @@ int run_launchable(const mxd_image* images, int32_t n, int32_t out_dtype, int32_
 }  // namespace
 
 int prepare_post_ops(const mxd_image* images, int32_t n, PostOps* ops, int32_t* out_dtype, mxd_out_format* f32_fmt) {
-  if (!ops->per_image()) return MXD_OK;
+  if (!ops->per_image() && !ops->erases) return MXD_OK;
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
+  if (ops->erases) {
+    // (against the elements the call writes, before the format below stands in for MXD_F32_DIV255)
+    if (!ops->fmt && *out_dtype != MXD_U8 && *out_dtype != MXD_F32_DIV255) return fail(MXD_ERR_INVALID, "mxd: bad out_dtype");
+    if (int rc = erase_validate(images, ops->erases, n, erase_elem(ops->fmt, *out_dtype))) return rc;
+    if (!ops->per_image()) return MXD_OK;
+  }
   if (ops->warps)
     if (int rc = warp_validate(images, ops->warps, n)) return rc;
   if (ops->enhances)

@@ -463,6 +463,53 @@ void append_blurs(Batch& b, const PostOps& ops) {
   std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.blur_at), recs.data(), recs.size() * sizeof(mxd::BlurRecDev));
 }
 
+// The erase table, behind everything else of the upload and only when some
+// image is erased: one record per non-empty box, in batch order.  Seeds, boxes
+// and fills are part of the upload's bytes, so a cached slot is reused only
+// for an identical erase.
+int append_erases(Batch& b, const mxd_image* callers, const PostOps& ops, int32_t elem) {
+  BatchLayout& L = b.L;
+  std::vector<mxd::EraseRecDev> recs;
+  int64_t units = 0;
+  const bool chw = ops.fmt && ops.fmt->layout == MXD_LAYOUT_CHW;
+  for (int32_t i = 0; i < b.n; i++) {
+    const mxd_erase& e = ops.erases[i];
+    for (int32_t k = 0; k < e.count; k++) {
+      const int32_t* bx = e.box[k];
+      if (bx[0] >= bx[2] || bx[1] >= bx[3]) continue;  // an empty box writes nothing
+      mxd::EraseRecDev r{};
+      r.dst = callers[i].dst;
+      r.dst_stride = callers[i].dst_stride;
+      r.plane_stride = chw ? ops.fmt->plane_stride : 0;
+      r.x0 = bx[0], r.y0 = bx[1], r.x1 = bx[2], r.y1 = bx[3];
+      for (int32_t l = k + 1; l < e.count; l++) std::memcpy(r.later[l - k - 1], e.box[l], sizeof r.later[0]);
+      r.unit_begin = (int32_t)units;
+      r.nq = ((bx[2] - 1) >> 2) - (bx[0] >> 2) + 1;
+      r.nq_recip = r.nq == 1 ? 0xffffffffu : (uint32_t)(((uint64_t)1 << 32) / (uint32_t)r.nq);
+      const int64_t items = (int64_t)(bx[3] - bx[1]) * r.nq;
+      units += (items + mxd::kEraseItems - 1) / mxd::kEraseItems;
+      // (items below 2^31: the reciprocal's quotient is then at most one short)
+      if (items > INT32_MAX || units > INT32_MAX)
+        return fail(MXD_ERR_UNSUPPORTED, "mxd_erase: the boxes of one call exceed 2^31 quads");
+      r.items = (int32_t)items;
+      r.pixel = e.mode == MXD_ERASE_PIXEL ? 1 : 0;
+      r.box_no = (uint32_t)k;
+      if (r.pixel) r.seed[0] = e.seed[0], r.seed[1] = e.seed[1];
+      erase_fill(e, k, elem, r.fill);
+      recs.push_back(r);
+    }
+  }
+  if (recs.empty()) return MXD_OK;
+  L.erase_at = L.descs.size();
+  L.erase_count = (int32_t)recs.size();
+  L.erase_units = (int32_t)units;
+  L.erase_elem = elem;
+  L.erase_chw = chw;
+  L.descs.resize(L.erase_at + (recs.size() * sizeof(mxd::EraseRecDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+  std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.erase_at), recs.data(), recs.size() * sizeof(mxd::EraseRecDev));
+  return MXD_OK;
+}
+
 // The mix stage's own fields: partners, ops, weights and boxes are part of the
 // upload's bytes, so a cached slot is reused only for equal mixes.  The
 // partner's rows are those the partner's own entry reads (an offset into the
@@ -609,6 +656,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   // alignment, and an image they do not take is resized into u8 scratch rows
   // (16-byte aligned; placed once the plans are known).
   const mxd_image* const callers = images;
+  const int32_t caller_dtype = out_dtype;
   // A colour or tone call plans every image so, and keeps every u8 kernel a
   // plain u8 call has (the cubic filters' and JPEG plane sources' wave
   // kernels too).
@@ -633,6 +681,8 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = general_group(b)) return rc;
   append_tables(b);
   append_stages(b, callers, ops);
+  if (ops.erases)
+    if (int rc = append_erases(b, callers, ops, erase_elem(ops.fmt, caller_dtype))) return rc;
   // Largest first (a band unit is a workgroup, ~4 wave units).
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});

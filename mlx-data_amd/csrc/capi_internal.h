@@ -270,10 +270,17 @@ LayoutEnv host_env(int32_t band_capacity, int32_t wave_capacity);
 // enhances: an enhance call, enhances[i] belongs to images[i]; every other
 // member may be null then.  mixes: a mix call, mixes[i] belongs to images[i] and
 // names its partner among the call's images; every other member may be null
-// then.
+// then.  erases: an erase call, erases[i] belongs to images[i]; every other
+// member may be null then.  The erases change nothing of what the call plans,
+// uploads and launches otherwise (they are no part of any() and per_image()):
+// the erase launch (erase.hip) follows the stage that writes the destinations
+// and rewrites output elements in place.  It reads no rows, and its records
+// are one per box rather than per image, so it is no member of the chain below:
+// its table lies behind every stage's entries (BatchLayout::erase_at).
 //
 // The stage chain.  Behind its resize kernels such a call launches at most
-// four stages, in this order: the warp stage (warp.hip; a warp call), the
+// four stages (and, in an erase call, the erase launch behind the last of
+// them, which is no stage: see above), in this order: the warp stage (warp.hip; a warp call), the
 // enhance stage (enhance.hip; an enhance call), the second pass
 // (row_stage.hip: format_rows for the images of a formatted call that no wave
 // kernel takes; pixel_rows for every image of a colour or tone call, and,
@@ -297,10 +304,12 @@ struct PostOps {
   const mxd_warp* warps = nullptr;
   const mxd_enhance* enhances = nullptr;
   const mxd_mix* mixes = nullptr;
+  const mxd_erase* erases = nullptr;
   // (a format alone, or nullptr, converts: a formatted / plain call)
   PostOps(const mxd_out_format* f = nullptr, const mxd_color* c = nullptr, const mxd_tone* t = nullptr,
-          const mxd_warp* w = nullptr, const mxd_enhance* e = nullptr, const mxd_mix* m = nullptr)
-      : fmt(f), colors(c), tones(t), warps(w), enhances(e), mixes(m) {}
+          const mxd_warp* w = nullptr, const mxd_enhance* e = nullptr, const mxd_mix* m = nullptr,
+          const mxd_erase* er = nullptr)
+      : fmt(f), colors(c), tones(t), warps(w), enhances(e), mixes(m), erases(er) {}
   bool any() const { return fmt || colors || tones || warps || enhances || mixes; }
   bool per_image() const { return colors || tones || warps || enhances || mixes; }  // a colour, tone, warp, enhance or mix call
   SecondPass pass() const {
@@ -319,7 +328,8 @@ struct PostOps {
   PostOps at(int32_t first) const {
     return PostOps{fmt, colors ? colors + first : nullptr, tones ? tones + first : nullptr,
                    warps ? warps + first : nullptr, enhances ? enhances + first : nullptr,
-                   mixes ? mixes + first : nullptr};  // (a mix call is one chunk: partners index from `first` = 0)
+                   mixes ? mixes + first : nullptr,  // (a mix call is one chunk: partners index from `first` = 0)
+                   erases ? erases + first : nullptr};
   }
 };
 
@@ -404,6 +414,13 @@ struct BatchLayout {
   // every stage's entries, for blur_units workgroups; none without a blurred image.
   size_t blur_at = 0;
   int32_t blur_count = 0, blur_units = 0;
+  // The erase table (erase.hip): erase_count records (one per non-empty box)
+  // from block erase_at, behind every stage's entries and the blur table, for
+  // erase_units workgroups writing erase_elem (mxd_erase_elem) elements, CHW or
+  // not; none without an erased image.
+  size_t erase_at = 0;
+  int32_t erase_count = 0, erase_units = 0, erase_elem = 0;
+  bool erase_chw = false;
   bool mixed() const { return stage(StageKind::Mix) != nullptr; }
   size_t mix_at() const { return mixed() ? stage(StageKind::Mix)->at : 0; }
   int32_t mix_blocks() const { return mixed() ? stage(StageKind::Mix)->blocks : 0; }
@@ -501,6 +518,16 @@ extern std::atomic<int32_t> g_blur_seg_rows, g_blur_step;
 // MixUp / CutMix (mix.cpp).
 // mixes[i] against images[i] and its partner's (images may be null: the entries alone).
 int mix_validate(const mxd_image* images, const mxd_mix* mixes, int32_t n);
+
+// ---------------------------------------------------------------------------
+// Random Erasing (erase.cpp).
+// The element type (mxd_erase_elem) a call with this format and out_dtype writes.
+int32_t erase_elem(const mxd_out_format* fmt, int32_t out_dtype);
+// erases[i] against images[i] (images may be null: the entries alone) for `elem` elements.
+int erase_validate(const mxd_image* images, const mxd_erase* erases, int32_t n, int32_t elem);
+// Box b's per-channel fill as element bits (CONST: the cast values; COLOR: its
+// normals; PIXEL: zeros, not read).
+void erase_fill(const mxd_erase& e, int32_t b, int32_t elem, uint32_t fill[3]);
 
 // ---------------------------------------------------------------------------
 // Formatted outputs (outfmt.cpp).

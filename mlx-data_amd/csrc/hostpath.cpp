@@ -695,12 +695,13 @@ int host_path(const mxd_image* images, int32_t n, int32_t out_dtype, int32_t dev
               const mxd_jpeg_image* jpeg, PostOps ops) {
   if (n < 0 || (n > 0 && !images)) return fail(MXD_ERR_INVALID, "mxd: bad image array");
   // the stages behind the resize write device destinations only
-  const char* const call = ops.mixes      ? "mix"
+  const char* const call = ops.erases     ? "erase"
+                           : ops.mixes    ? "mix"
                            : ops.warps    ? "warp"
                            : ops.enhances ? "enhance"
                            : ops.tones    ? "tone"
                                           : "colour";
-  if (!dst_device && ops.per_image())
+  if (!dst_device && (ops.per_image() || ops.erases))
     return fail(MXD_ERR_UNSUPPORTED, std::string("mxd: ") + call + " calls need device destinations");
   mxd_out_format f32_fmt;
   if (int rc = prepare_post_ops(images, n, &ops, &out_dtype, &f32_fmt)) return rc;

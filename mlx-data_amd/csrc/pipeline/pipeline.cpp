@@ -264,8 +264,11 @@ struct Share {
   std::vector<mxd_tone> tones;
   std::vector<mxd_warp> warps;
   std::vector<mxd_enhance> enhances;
-  void add(const Img& im, const mxd_color& c, const mxd_tone& t, const mxd_warp& w, const mxd_enhance& e) {
+  std::vector<mxd_erase> erases;
+  void add(const Img& im, const mxd_color& c, const mxd_tone& t, const mxd_warp& w, const mxd_enhance& e,
+           const mxd_erase& er) {
     images.push_back(im), colors.push_back(c), tones.push_back(t), warps.push_back(w), enhances.push_back(e);
+    erases.push_back(er);
   }
 };
 
@@ -278,7 +281,7 @@ J for_source(const mxd_jpeg_image*, P, J jpeg) { return jpeg; }
 // What some plan of a launch has: the whole launch then goes through that
 // member's calls, plans without one with the identity / MXD_*_NONE (exact).
 struct Members {
-  bool colored = false, toned = false, warped = false, enhanced = false;
+  bool colored = false, toned = false, warped = false, enhanced = false, erased = false;
 };
 
 // One call for a share: the entry point of the last stage some plan has
@@ -294,6 +297,9 @@ int call_abi(const Share<Img>& s, const Members& m, int32_t dtype, const mxd_out
   const mxd_color* c = m.colored ? s.colors.data() : nullptr;
   const mxd_tone* t = m.toned ? s.tones.data() : nullptr;
   const mxd_warp* w = m.warped ? s.warps.data() : nullptr;
+  if (m.erased)  // (erases are the last member: every other one may be null)
+    return for_source(im, mxd_resize_crop_to_device_erase, mxd_jpeg_resize_crop_to_device_erase)(
+        im, w, m.enhanced ? s.enhances.data() : nullptr, t, c, mixes, s.erases.data(), n, dtype, of, device);
   if (mixes)
     return for_source(im, mxd_resize_crop_to_device_mix, mxd_jpeg_resize_crop_to_device_mix)(
         im, w, m.enhanced ? s.enhances.data() : nullptr, t, c, mixes, n, dtype, of, device);
@@ -339,17 +345,20 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
     mxd_enhance e{};  // (MXD_ENHANCE_NONE for a plan without an enhance op)
     if (j.plan.enhanced) e.op = j.plan.enhance_op, e.factor = j.plan.enhance_factor, e.reserved[0] = j.plan.enhance_ksize;
     m.enhanced = m.enhanced || j.plan.enhanced;
+    const mxd_erase er = j.plan.erased ? j.plan.erase : mxd_erase{};  // (count 0 for a plan that is not erased)
+    m.erased = m.erased || j.plan.erased;
     if (auto src = j.plan.src->jpeg()) {
-      jp.add(jpeg_desc(j.plan, *src, j.dst, j.stride), c, t, w, e);
+      jp.add(jpeg_desc(j.plan, *src, j.dst, j.stride), c, t, w, e, er);
       keep.push_back(std::move(src));
     } else {
-      plain.add(plan_desc(j.plan, j.dst, j.stride), c, t, w, e);
+      plain.add(plan_desc(j.plan, j.dst, j.stride), c, t, w, e, er);
     }
   }
   g_run_jpeg.fetch_add((int64_t)jp.images.size());
   // Per-image members and formatted outputs: device destinations only
   // (mxd_*_to_device_*); a formatted launch for host destinations is none.
   if (const char* what = mixes        ? "a mix"
+                         : m.erased   ? "an erase"
                          : m.enhanced ? "an enhance"
                          : m.warped   ? "a warp"
                          : m.toned    ? "a tone"
@@ -388,11 +397,19 @@ int run_on(const Job* jobs, size_t n, int32_t dtype, int device, bool dst_device
       d.channels = 3;
       d.dst = jobs[i].dst, d.dst_stride = jobs[i].stride;
     }
-    if (int rc = call_abi(jp, m, MXD_U8, nullptr, device, true)) return rc;
-    if (int rc = call_abi(plain, m, MXD_U8, nullptr, device, true)) return rc;
+    // (the erases act on the output elements: they go with the mix call, in batch order)
+    std::vector<mxd_erase> erases;
+    for (size_t i = 0; i < n && m.erased; i++) erases.push_back(jobs[i].plan.erased ? jobs[i].plan.erase : mxd_erase{});
+    Members unerased = m;
+    unerased.erased = false;
+    if (int rc = call_abi(jp, unerased, MXD_U8, nullptr, device, true)) return rc;
+    if (int rc = call_abi(plain, unerased, MXD_U8, nullptr, device, true)) return rc;
     // (the two calls above are synchronous: the block is written)
-    if (int rc = mxd_resize_crop_batch_mix(crops.data(), nullptr, nullptr, nullptr, nullptr, mixes, (int32_t)n, dtype,
-                                           fmt ? &of : nullptr, device, nullptr))
+    if (int rc = m.erased ? mxd_resize_crop_batch_erase(crops.data(), nullptr, nullptr, nullptr, nullptr, mixes,
+                                                        erases.data(), (int32_t)n, dtype, fmt ? &of : nullptr, device,
+                                                        nullptr)
+                          : mxd_resize_crop_batch_mix(crops.data(), nullptr, nullptr, nullptr, nullptr, mixes, (int32_t)n,
+                                                      dtype, fmt ? &of : nullptr, device, nullptr))
       return rc;
     return mxd_device_synchronize(device);
   }
@@ -559,7 +576,7 @@ void run_host(const std::vector<Job>& jobs, int32_t dtype, const OutFormat* fmt 
   // a coloured plan anywhere: every slice takes the device call and one copy
   // back, like a formatted batch (each slice carries its own jobs' matrices)
   bool colored = false;  // (or toned, warped or enhanced: device calls only, too)
-  for (const Job& j : jobs) colored = colored || j.plan.colored || j.plan.toned || j.plan.warped || j.plan.enhanced;
+  for (const Job& j : jobs) colored = colored || j.plan.colored || j.plan.toned || j.plan.warped || j.plan.enhanced || j.plan.erased;
   auto slice = [&jobs, dtype, &devs, &sl, fmt, colored](size_t s) -> std::string {
     const Job* first = jobs.data() + sl[s].begin;
     const size_t count = (size_t)(sl[s].end - sl[s].begin);
@@ -735,7 +752,10 @@ namespace {
 // the identity plan over all of it.
 ImagePlan view(const std::shared_ptr<Array>& img) {
   if (img->type() != DType::UInt8) throw std::invalid_argument("image must be of type UInt8");
-  if (img->plan() && img->pending()) return *img->plan();
+  if (img->plan() && img->pending()) {
+    if (!img->plan()->erased) return *img->plan();
+    img->data();  // an erase is the launch's last step: run it, the op works on its bytes
+  }
   ImagePlan p;
   p.src = img;
   p.sw = p.resize_w = p.crop_w = img->shape(1);
@@ -1246,6 +1266,94 @@ std::shared_ptr<Array> ImageAffine::apply_video(const std::shared_ptr<Array>& vi
   const std::vector<double> v = params();
   std::vector<std::shared_ptr<Array>> frames;
   for (int64_t i = 0; i < video->shape(0); i++) frames.push_back(mark(video_frame(video, i), v));
+  if (frames.empty()) throw std::runtime_error("applyVideo: empty video");
+  return stack_frames(frames);
+}
+
+// ---- Random Erasing: mark the plan ----------------------------------------------
+int32_t parse_erase_mode(const std::string& mode) {
+  if (mode == "const") return MXD_ERASE_CONST;
+  if (mode == "rand") return MXD_ERASE_COLOR;
+  if (mode == "pixel") return MXD_ERASE_PIXEL;
+  throw std::invalid_argument("image_random_erasing: mode must be const, rand or pixel, not '" + mode + "'");
+}
+
+void check_erase_spec(const EraseSpec& s) {
+  const char* what = "image_random_erasing: ";
+  if (!(s.prob >= 0.0 && s.prob <= 1.0)) throw std::invalid_argument(std::string(what) + "prob must be in 0..1");
+  if (!(s.area_lo > 0.0 && s.area_lo <= s.area_hi && s.area_hi <= 1.0))
+    throw std::invalid_argument(std::string(what) + "area needs 0 < lo <= hi <= 1");
+  if (!(s.aspect_lo > 0.0 && s.aspect_lo <= s.aspect_hi && std::isfinite(s.aspect_hi)))
+    throw std::invalid_argument(std::string(what) + "aspect needs 0 < lo <= hi");
+  if (s.mode < MXD_ERASE_CONST || s.mode > MXD_ERASE_PIXEL) throw std::invalid_argument(std::string(what) + "unknown mode");
+  if (!(1 <= s.count_lo && s.count_lo <= s.count_hi && s.count_hi <= MXD_ERASE_MAX_BOXES))
+    throw std::invalid_argument(std::string(what) + "count must be in 1..4 (lo <= hi)");
+  if (!std::isfinite(s.value)) throw std::invalid_argument(std::string(what) + "value must be finite");
+}
+
+mxd_erase random_erasing_draws(int64_t h, int64_t w, const EraseSpec& s) {
+  mxd_erase e{};
+  auto st = get_state();
+  if (!(std::uniform_real_distribution<double>(0.0, 1.0)(st->gen) <= s.prob)) return e;
+  const int32_t count = s.count_lo == s.count_hi ? s.count_lo : std::uniform_int_distribution<int32_t>(s.count_lo, s.count_hi)(st->gen);
+  e.mode = s.mode;
+  for (int c = 0; c < 3; c++) e.value[c] = s.mode == MXD_ERASE_CONST ? s.value : 0.0f;
+  for (int32_t b = 0; b < count; b++)
+    for (int attempt = 0; attempt < 10; attempt++) {
+      const double target = std::uniform_real_distribution<double>(s.area_lo, s.area_hi)(st->gen) * (double)(h * w) / count;
+      const double ratio = std::exp(std::uniform_real_distribution<double>(std::log(s.aspect_lo), std::log(s.aspect_hi))(st->gen));
+      const int64_t bh = std::lround(std::sqrt(target * ratio)), bw = std::lround(std::sqrt(target / ratio));
+      if (!(bw < w && bh < h)) continue;
+      const int64_t top = std::uniform_int_distribution<int64_t>(0, h - bh)(st->gen);
+      const int64_t left = std::uniform_int_distribution<int64_t>(0, w - bw)(st->gen);
+      int32_t* bx = e.box[e.count++];
+      bx[0] = (int32_t)left, bx[1] = (int32_t)top, bx[2] = (int32_t)(left + bw), bx[3] = (int32_t)(top + bh);
+      break;
+    }
+  if (s.mode != MXD_ERASE_CONST) e.seed[0] = (uint32_t)st->gen(), e.seed[1] = (uint32_t)st->gen();
+  return e;
+}
+
+ImageRandomErasing::ImageRandomErasing(std::string ikey, const EraseSpec& spec, std::string okey)
+    : ImageOp(std::move(ikey), std::move(okey)), spec_(spec) {
+  check_erase_spec(spec_);
+}
+
+std::shared_ptr<Array> ImageRandomErasing::mark(const std::shared_ptr<Array>& img, const mxd_erase& e) const {
+  // a pending plan as it is, marked f32 / formatted or not (the op acts on output elements)
+  const bool pending = img->plan() && img->pending();
+  if (pending && img->plan()->erased && img->type() != DType::UInt8)
+    throw std::runtime_error("image_random_erasing: the image is erased already (one erase per formatted image)");
+  const bool u8 = img->type() == DType::UInt8;
+  if (!u8 && !pending) throw std::invalid_argument("image must be of type UInt8");
+  ImagePlan p = u8 ? view(img) : *img->plan();
+  if (p.channels() != 3)
+    throw std::runtime_error("image_random_erasing: image must have 3 channels, not " + std::to_string(p.channels()));
+  if (u8 && spec_.mode != MXD_ERASE_CONST)
+    throw std::runtime_error("image_random_erasing: mode rand / pixel writes normals: mark the image with image_to_float or "
+                             "image_normalize first");
+  if (u8 && !(spec_.value >= 0.0f && spec_.value <= 255.0f && spec_.value == std::floor(spec_.value)))
+    throw std::runtime_error("image_random_erasing: value must be an integer in 0..255 on a uint8 image");
+  if (e.count == 0) return pending ? img : make(p);
+  p.erased = true;
+  p.erase = e;
+  return make(p);
+}
+
+std::shared_ptr<Array> ImageRandomErasing::apply_key(const std::shared_ptr<Array>& x) const {
+  if (x->ndim() == 3 && x->plan() && x->pending() && x->plan()->formatted && x->plan()->out.chw()) return apply_image(x);
+  return ImageOp::apply_key(x);
+}
+
+std::shared_ptr<Array> ImageRandomErasing::apply_image(const std::shared_ptr<Array>& img) const {
+  const bool chw = img->plan() && img->pending() && img->plan()->formatted && img->plan()->out.chw();
+  return mark(img, random_erasing_draws(img->shape(chw ? 1 : 0), img->shape(chw ? 2 : 1), spec_));
+}
+
+std::shared_ptr<Array> ImageRandomErasing::apply_video(const std::shared_ptr<Array>& video) const {
+  const mxd_erase e = random_erasing_draws(video->shape(1), video->shape(2), spec_);
+  std::vector<std::shared_ptr<Array>> frames;
+  for (int64_t i = 0; i < video->shape(0); i++) frames.push_back(mark(video_frame(video, i), e));
   if (frames.empty()) throw std::runtime_error("applyVideo: empty video");
   return stack_frames(frames);
 }

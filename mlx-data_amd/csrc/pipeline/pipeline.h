@@ -137,6 +137,13 @@ struct ImagePlan {
   int32_t enhance_op = 0;
   float enhance_factor = 1.0f;
   int32_t enhance_ksize = 0;  // GAUSSIAN_BLUR only
+  // image_random_erasing: the launch fills erase.box[0..count) of the output
+  // elements last, behind the output form (mxd_erase: Random Erasing).  It is
+  // the one image op accepted on a plan already marked f32 / formatted, since
+  // it acts on output elements; any image op after it on a u8 plan
+  // materialises the plan first.
+  bool erased = false;
+  mxd_erase erase{};
   int64_t channels() const;
 };
 
@@ -565,6 +572,42 @@ struct DeviceOut {
   int device = -1;
   std::vector<std::string> keys;
 };
+// image_random_erasing (an addition to the reference's surface): timm's
+// RandomErasing on the output elements, inside the batch launch (DESIGN.md
+// sections 1g, 5n).  mode: const (value), rand (one normal per box and
+// channel) or pixel (one normal per element); rand and pixel need a plan marked
+// by image_to_float / image_normalize.  Bad ranges, an unknown mode or a count
+// outside 1..4 throw std::invalid_argument when the op is made.
+struct EraseSpec {
+  double prob = 0.5, area_lo = 0.02, area_hi = 1.0 / 3.0, aspect_lo = 0.3, aspect_hi = 1.0 / 0.3;
+  int32_t mode = MXD_ERASE_CONST, count_lo = 1, count_hi = 1;
+  float value = 0.0f;
+};
+void check_erase_spec(const EraseSpec& spec);
+int32_t parse_erase_mode(const std::string& mode);
+// The draws for one h x w image from the thread's State, with freshly
+// constructed libstdc++ distributions: one uniform_real<double>(0, 1), erased
+// iff it is <= prob (nothing more is drawn otherwise); the count when lo != hi
+// (uniform_int); per box up to 10 attempts of target = uniform(area) h w /
+// count, ratio = exp(uniform(log aspect)), bh = lround(sqrt(target ratio)), bw
+// = lround(sqrt(target / ratio)), taken iff bw < w && bh < h with top =
+// uniform_int(0, h - bh), left = uniform_int(0, w - bw); for rand / pixel two
+// generator words as the seed.  count 0: not erased.
+mxd_erase random_erasing_draws(int64_t h, int64_t w, const EraseSpec& spec);
+
+class ImageRandomErasing : public ImageOp {
+ public:
+  ImageRandomErasing(std::string ikey, const EraseSpec& spec, std::string okey);
+  std::shared_ptr<Array> apply_image(const std::shared_ptr<Array>& img) const override;
+  std::shared_ptr<Array> apply_video(const std::shared_ptr<Array>& video) const override;  // one draw for all frames
+  // (a pending image already marked chw has the shape (C, H, W): it skips ImageOp's (H, W, C) checks)
+  std::shared_ptr<Array> apply_key(const std::shared_ptr<Array>& x) const override;
+
+ private:
+  std::shared_ptr<Array> mark(const std::shared_ptr<Array>& img, const mxd_erase& e) const;
+  EraseSpec spec_;
+};
+
 // batch_mix: MixUp / CutMix across the images of `key` in a batch (timm's
 // FastCollateMixup).  The partner of image i of n is
 // n - 1 - i.  mode: one draw set per batch, per pair (i < ceil(n / 2), shared by

@@ -376,6 +376,32 @@ std::shared_ptr<ImageAffine> random_affine_op(const char* op, const std::string&
 }
 
 // The random enhance ops' factor: a (lo, hi) pair.
+// image_random_erasing's arguments: count is 1..4 or a (lo, hi) pair.
+EraseSpec erase_spec(double prob, std::pair<double, double> area, std::pair<double, double> aspect, const std::string& mode,
+                     const py::object& count, double value) {
+  EraseSpec s;
+  s.prob = prob, s.area_lo = area.first, s.area_hi = area.second, s.aspect_lo = aspect.first, s.aspect_hi = aspect.second;
+  s.mode = parse_erase_mode(mode);
+  try {
+    if (py::isinstance<py::int_>(count)) s.count_lo = s.count_hi = count.cast<int32_t>();
+    else std::tie(s.count_lo, s.count_hi) = count.cast<std::pair<int32_t, int32_t>>();
+  } catch (const py::cast_error&) {
+    throw std::invalid_argument("image_random_erasing: count must be an int or a (lo, hi) pair");
+  }
+  s.value = (float)value;
+  check_erase_spec(s);
+  return s;
+}
+
+// An erase as _plan and _random_erasing_draws report it: None, or (mode, boxes, seed).
+py::object erase_entry(const mxd_erase& e) {
+  if (e.count == 0) return py::none();
+  static const char* const names[] = {"const", "rand", "pixel"};
+  py::list boxes;
+  for (int32_t b = 0; b < e.count; b++) boxes.append(py::make_tuple(e.box[b][0], e.box[b][1], e.box[b][2], e.box[b][3]));
+  return py::make_tuple(names[e.mode], boxes, py::make_tuple(e.seed[0], e.seed[1]));
+}
+
 std::pair<double, double> enhance_range(const std::string& op, const py::object& v) {
   try {
     return v.cast<std::pair<double, double>>();
@@ -622,6 +648,17 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
           },
           py::arg("key"), py::arg("factor"), py::arg("output_key") = "")
       .def(
+          "image_random_erasing",
+          [wrap](const Self& self, const std::string& key, double prob, std::pair<double, double> area,
+                 std::pair<double, double> aspect, const std::string& mode, const py::object& count, double value,
+                 const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageRandomErasing>(key, erase_spec(prob, area, aspect, mode, count, value),
+                                                                   output_key));
+          },
+          py::arg("key"), py::arg("prob") = 0.5, py::arg("area") = std::make_pair(0.02, 1.0 / 3.0),
+          py::arg("aspect") = std::make_pair(0.3, 1.0 / 0.3), py::arg("mode") = "const", py::arg("count") = 1,
+          py::arg("value") = 0.0, py::arg("output_key") = "")
+      .def(
           "image_gaussian_blur",
           [wrap](const Self& self, const std::string& key, int32_t kernel_size, double sigma, const std::string& output_key) {
             return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_GAUSSIAN_BLUR, sigma, output_key, kernel_size));
@@ -854,6 +891,15 @@ PYBIND11_MODULE(_pipeline, m) {
   // diagnostics (device-free): the entries batch_mix would give a batch of n images of h x w pixels, drawn
   // from the calling thread's State: (op, partner, w_self, w_other, x0, y0, x1, y1, lam) per image
   m.def(
+      "_random_erasing_draws",
+      [](int64_t h, int64_t w, double prob, std::pair<double, double> area, std::pair<double, double> aspect,
+         const std::string& mode, const py::object& count, double value) {
+        return erase_entry(random_erasing_draws(h, w, erase_spec(prob, area, aspect, mode, count, value)));
+      },
+      py::arg("h"), py::arg("w"), py::arg("prob") = 0.5, py::arg("area") = std::make_pair(0.02, 1.0 / 3.0),
+      py::arg("aspect") = std::make_pair(0.3, 1.0 / 0.3), py::arg("mode") = "const", py::arg("count") = 1,
+      py::arg("value") = 0.0);
+  m.def(
       "_batch_mix_draws",
       [](int64_t n, int64_t h, int64_t w, double mixup_alpha, double cutmix_alpha, double prob, double switch_prob,
          const std::string& mode) {
@@ -986,6 +1032,7 @@ PYBIND11_MODULE(_pipeline, m) {
       d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor), p.enhance_ksize);
     else if (p.enhanced) d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor));
     else d["enhance"] = py::none();
+    d["erase"] = p.erased ? erase_entry(p.erase) : py::object(py::none());
     return d;
   });
 }

@@ -325,6 +325,35 @@ struct MixRowDev {
 };
 static_assert(sizeof(MixRowDev) == 96, "MixRowDev layout");
 int launch_mix(const MixRowDev* rows, int nimgs, int nblocks, const OutFmtDev& fmt, void* stream);
+// The erase launch (erase.hip): the last launch of an erase call (mxd_erase),
+// behind the stage that writes the destinations.  It reads no rows and writes
+// output elements in place, so it has no RowHead and no scratch: one record
+// per non-empty box, in a table of its own behind every stage's entries (the
+// BlurRecDev pattern; none when no image is erased).  A unit (a workgroup) is
+// kEraseItems consecutive items of a box's quad grid -- rows y0..y1 times the
+// image-aligned x-quads x0 >> 2 .. (x1 - 1) >> 2 -- units numbered through
+// unit_begin.  Seeds, boxes and fills are part of the uploaded bytes, so a
+// cached descriptor slot serves an identical erase only.
+constexpr int kEraseItems = 256;
+struct EraseRecDev {
+  void* dst;                 // the image's destination (element aligned)
+  int64_t dst_stride;        // bytes between rows
+  int64_t plane_stride;      // CHW: bytes between channel planes (0 for HWC)
+  int32_t x0, y0, x1, y1;    // the box, within the crop window and not empty
+  int32_t later[3][4];       // the image's boxes of higher number (x0, y0, x1, y1; zeros: none): they win
+  int32_t unit_begin;        // first of the box's workgroups among the launch's
+  int32_t nq;                // quads per row of the grid
+  uint32_t nq_recip;         // floor(2^32 / nq) (nq == 1: 2^32 - 1): item / nq is mulhi or one more
+  int32_t items;             // rows * nq
+  int32_t pixel;             // 1: per-element noise; 0: the constants below (CONST, COLOR)
+  uint32_t box_no;           // the box's number in its image (the Philox counter's fourth word)
+  uint32_t seed[2];          // the Philox key
+  uint32_t fill[3];          // per-channel fill as element bits
+  int32_t pad;
+};
+static_assert(sizeof(EraseRecDev) == 136, "EraseRecDev layout");
+// elem: noise::Elem (erase_noise.h); chw: channel planes.
+int launch_erase(const EraseRecDev* recs, int nrecs, int nunits, int elem, bool chw, void* stream);
 // What the entries of every stage behind the resize begin with: the rows the
 // stage reads and writes.  The host places them by one rule for all stages
 // (capi_internal.h, the stage chain); the rest of an entry is its stage's own.

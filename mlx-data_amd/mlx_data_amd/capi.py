@@ -53,6 +53,8 @@ EXPORTS = (
     "mxd_resize_crop_to_device_enhance", "mxd_jpeg_resize_crop_to_device_enhance",
     "mxd_mix_validate", "mxd_mix_apply_u8", "mxd_resize_crop_batch_mix", "mxd_resize_crop_to_device_mix",
     "mxd_jpeg_resize_crop_to_device_mix",
+    "mxd_erase_validate", "mxd_erase_apply", "mxd_erase_normals", "mxd_resize_crop_batch_erase",
+    "mxd_resize_crop_to_device_erase", "mxd_jpeg_resize_crop_to_device_erase",
 )
 
 MXD_ELEM_F32 = 0
@@ -626,6 +628,96 @@ def jpeg_resize_crop_to_device_mix(images, warps, enhances, tones, colors, mixes
                                    device=0):
     check(lib().mxd_jpeg_resize_crop_to_device_mix(images, warps, enhances, tones, colors, mixes, n, out_dtype,
                                                    _fmt_ref(fmt), device))
+
+
+MXD_ERASE_CONST = 0
+MXD_ERASE_COLOR = 1
+MXD_ERASE_PIXEL = 2
+MXD_ERASE_U8 = 0
+MXD_ERASE_F32 = 1
+MXD_ERASE_F16 = 2
+MXD_ERASE_BF16 = 3
+MXD_ERASE_MAX_BOXES = 4
+
+
+class MxdErase(ctypes.Structure):
+    """struct mxd_erase (include/mxd_amd.h): the box count (0: not erased), the mode, the
+    Philox key, CONST's per-channel values, up to four boxes x0, y0, x1, y1, reserved words (0)."""
+
+    _fields_ = [("count", ctypes.c_int32), ("mode", ctypes.c_int32), ("seed", ctypes.c_uint32 * 2),
+                ("value", ctypes.c_float * 4), ("box", (ctypes.c_int32 * 4) * MXD_ERASE_MAX_BOXES),
+                ("reserved", ctypes.c_int32 * 8)]
+
+
+def make_erases(erases):
+    """Entries -> ctypes array of mxd_erase.  An entry is an MxdErase, None (not erased) or
+    (mode, boxes, seed, value): boxes a list of (x0, y0, x1, y1), seed two 32-bit words (or
+    None), value a float or three (default 0)."""
+    arr = (MxdErase * max(1, len(erases)))()
+    for i, e in enumerate(erases):
+        if isinstance(e, MxdErase):
+            arr[i] = e
+        if e is None or isinstance(e, MxdErase):
+            continue
+        mode, boxes = int(e[0]), list(e[1])
+        seed = e[2] if len(e) > 2 and e[2] is not None else (0, 0)
+        value = e[3] if len(e) > 3 else 0.0
+        arr[i].count, arr[i].mode = len(boxes), mode
+        arr[i].seed[0], arr[i].seed[1] = int(seed[0]), int(seed[1])
+        for c, v in enumerate(value if isinstance(value, (tuple, list)) else (value,) * 3):
+            arr[i].value[c] = float(v)
+        # (count is every box given, so that a fifth is refused; the struct holds four)
+        for b, box in enumerate(boxes[:MXD_ERASE_MAX_BOXES]):
+            for k in range(4):
+                arr[i].box[b][k] = int(box[k])
+    return arr
+
+
+def erase_validate(images, erases, elem, n=None):
+    """mxd_erase_validate: erases (entries as make_erases takes them) against an mxd_image
+    array, or None, for a call that writes `elem` (MXD_ERASE_U8 ...) elements."""
+    check(lib().mxd_erase_validate(images, make_erases(erases), len(erases) if n is None else n, int(elem)))
+
+
+def erase_normals(counter, key):
+    """mxd_erase_normals: (the four float32 normals, the four Philox4x32-10 words) of a counter and key."""
+    z, w = np.zeros(4, np.float32), np.zeros(4, np.uint32)
+    check(lib().mxd_erase_normals((ctypes.c_uint32 * 4)(*[int(v) for v in counter]),
+                                  (ctypes.c_uint32 * 2)(*[int(v) for v in key]), ctypes.c_void_p(z.ctypes.data),
+                                  ctypes.c_void_p(w.ctypes.data)))
+    return z, w
+
+
+def erase_apply(arr, erase, elem, chw=False):
+    """mxd_erase_apply: the CPU statement of an erase, in place, on one image held in a NumPy
+    array of the element's width (uint8, float32 / uint32, float16 / uint16): (h, w, 3), or
+    (3, h, w) with chw; rows and planes may be strided."""
+    c_ax, y_ax, x_ax = (0, 1, 2) if chw else (2, 0, 1)
+    es = arr.itemsize
+    assert arr.ndim == 3 and arr.shape[c_ax] == 3 and arr.strides[x_ax] == (es if chw else 3 * es)
+    assert chw or arr.strides[c_ax] == es
+    check(lib().mxd_erase_apply(ctypes.c_void_p(arr.ctypes.data), ctypes.c_int64(arr.strides[y_ax]),
+                                ctypes.c_int64(arr.strides[0] if chw else 0), arr.shape[x_ax], arr.shape[y_ax],
+                                int(elem), MXD_LAYOUT_CHW if chw else MXD_LAYOUT_HWC, make_erases([erase])))
+    return arr
+
+
+def resize_crop_batch_erase(images, warps, enhances, tones, colors, mixes, erases, n, out_dtype=MXD_U8, fmt=None,
+                            device=0, stream=None):
+    check(lib().mxd_resize_crop_batch_erase(images, warps, enhances, tones, colors, mixes, erases, n, out_dtype,
+                                            _fmt_ref(fmt), device, ctypes.c_void_p(stream)))
+
+
+def resize_crop_to_device_erase(images, warps, enhances, tones, colors, mixes, erases, n, out_dtype=MXD_U8, fmt=None,
+                                device=0):
+    check(lib().mxd_resize_crop_to_device_erase(images, warps, enhances, tones, colors, mixes, erases, n, out_dtype,
+                                                _fmt_ref(fmt), device))
+
+
+def jpeg_resize_crop_to_device_erase(images, warps, enhances, tones, colors, mixes, erases, n, out_dtype=MXD_U8,
+                                     fmt=None, device=0):
+    check(lib().mxd_jpeg_resize_crop_to_device_erase(images, warps, enhances, tones, colors, mixes, erases, n,
+                                                     out_dtype, _fmt_ref(fmt), device))
 
 
 def set_kernel_policy(policy):

@@ -151,6 +151,18 @@ for bit (``include/mxd_amd.h``).  It composes as ``image_sharpness`` does: a
 flip, tone and colour ops and the output forms after it; a crop, resize,
 ``image_rotate``, warp or second enhance op materialises what is pending.
 
+``image_random_erasing(key, prob=0.5, area=(0.02, 1/3), aspect=(0.3, 1/0.3),
+mode="const" | "rand" | "pixel", count=1 | (lo, hi), value=0.0,
+output_key="")`` (with ``image_random_erasing_if``) is timm's ``RandomErasing``
+inside the batch launch, on the output elements: the last step, behind
+``image_to_float`` / ``image_normalize``, and the one image op accepted after
+them.  ``rand`` / ``pixel`` write standard normals (Philox4x32-10, fixed bit for
+bit) and raise ``RuntimeError`` on a uint8 image that neither of those two ops
+has marked; ``const`` works anywhere.  The draws are timm's, from the
+``set_state`` generator (a video draws once); bad ranges, an unknown mode or a
+count outside 1..4 raise ``ValueError`` when the op is made.  Any image op after
+it on a uint8 image materialises what is pending.
+
 ``load_image`` decodes JPEG natively (``csrc/jpeg.cpp``, the reference's
 libjpeg path, ``core/image/ImageJPEG.cpp``).  With a device visible it only
 parses the markers of a sequential file and the batch launch runs the whole
@@ -226,7 +238,7 @@ def _add_if_variants(cls):
                  "image_random_translate", "image_random_affine_rotate",
                  "image_sharpness", "image_color", "image_brightness", "image_random_sharpness",
                  "image_random_color", "image_random_brightness", "image_gaussian_blur",
-                 "image_random_gaussian_blur"):
+                 "image_random_gaussian_blur", "image_random_erasing"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 
