@@ -21,7 +21,8 @@ tap builder (mlx-data_amd/csrc/taps.cpp):
    here with the host C compiler): vertical pass first in byte units, fmaf
    chains in tap order from 0, then the horizontal pass, then stbir's encode,
    over tap tables passed in (the product's, from mxd_axis_taps_filter) -- the
-   "bit-exact when the tables are shared" gate of the GPU kernels.
+   "bit-exact when the tables are shared" gate of the GPU kernels; and the
+   alpha-weighted STBIR_RGBA form of 4 channels in the same order.
 
 `run_device` runs images through mxd_resize_crop_batch with a filter each.
 """
@@ -180,9 +181,10 @@ def _tables(n_in, n_out, filter):
             np.ascontiguousarray(w, np.float32))
 
 
-def vfirst(img, g, filter):
+def vfirst(img, g, filter, rgba_weighted=False):
     """Kernel-order result of geometry g = (rw, rh, cx, cy, cw, ch, flip) with
-    the product's tap tables of `filter` (channels filtered independently)."""
+    the product's tap tables of `filter`: channels filtered independently, or
+    (rgba_weighted, 4 channels) the alpha-weighted STBIR_RGBA form."""
     img = np.ascontiguousarray(img, np.uint8)
     h, w, c = img.shape
     rw, rh, cx, cy, cw, ch, flip = g
@@ -190,6 +192,15 @@ def vfirst(img, g, filter):
     yf, yn, yw = _tables(h, rh, filter)
     out = np.zeros((ch, cw, c), np.uint8)
     i32, f32, u8 = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)
+    if rgba_weighted:
+        assert c == 4
+        rc = _vfirst_lib().filter_vfirst_rgba(
+            img.ctypes.data_as(u8), w, h, ctypes.c_int64(w * c), out.ctypes.data_as(u8),
+            xf.ctypes.data_as(i32), xn.ctypes.data_as(i32), xw.ctypes.data_as(f32), xw.shape[1],
+            yf.ctypes.data_as(i32), yn.ctypes.data_as(i32), yw.ctypes.data_as(f32), yw.shape[1],
+            cx, cy, cw, ch, int(flip))
+        assert rc == 0
+        return out
     rc = _vfirst_lib().filter_vfirst(
         img.ctypes.data_as(u8), w, h, c, ctypes.c_int64(w * c), out.ctypes.data_as(u8),
         xf.ctypes.data_as(i32), xn.ctypes.data_as(i32), xw.ctypes.data_as(f32), xw.shape[1],

@@ -65,3 +65,79 @@ int filter_vfirst(const uint8_t* src, int w, int h, int c, int64_t stride, uint8
   free(vrow);
   return 0;
 }
+
+/*
+ * The STBIR_RGBA (alpha-weighted) form of a 4-channel image over the same
+ * tables, in the order of oracle/stbir_oracle.c orc_resize_crop_vfirst_rgba:
+ * every byte decoded as b * (1/255), colours multiplied by their decoded
+ * alpha, the vertical then the horizontal pass (fmaf chains in tap order from
+ * 0), colours multiplied by 1 / filtered alpha unless that alpha is below
+ * stbir's small float (1 / 2^120) -- with a filter of negative lobes the
+ * filtered alpha can be negative: such a pixel keeps its premultiplied
+ * colours, negative ones included, and the encode's clamp bounds them --
+ * encoded as (uint8)trunc(clamp(v * 255 + 0.5)) with the multiply and the add
+ * unfused.  What the general HIP kernel's ALPHA form must give bit for bit.
+ */
+int filter_vfirst_rgba(const uint8_t* src, int w, int h, int64_t stride, uint8_t* dst, const int32_t* xfirst,
+                       const int32_t* xcount, const float* xw, int xwidth, const int32_t* yfirst, const int32_t* ycount,
+                       const float* yw, int ywidth, int cx, int cy, int cw, int ch, int flip) {
+  const int c = 4;
+  if (w <= 0 || h <= 0 || cw <= 0 || ch <= 0 || cx < 0 || cy < 0) return -1;
+  float* vrow = (float*)malloc(sizeof(float) * (size_t)w * c);
+  if (!vrow) return -1;
+  const float inv255 = 1.0f / 255.0f;
+  int xlo = xfirst[cx], xhi = xfirst[cx] + xcount[cx] - 1;
+  for (int ox = cx; ox < cx + cw; ox++) {
+    if (xfirst[ox] < xlo) xlo = xfirst[ox];
+    if (xfirst[ox] + xcount[ox] - 1 > xhi) xhi = xfirst[ox] + xcount[ox] - 1;
+  }
+  if (xlo < 0 || xhi >= w) {
+    free(vrow);
+    return -2;
+  }
+  for (int r = 0; r < ch; r++) {
+    const int oy = cy + r;
+    const int a = yfirst[oy], n = ycount[oy];
+    const float* cf = yw + (size_t)oy * ywidth;
+    if (a < 0 || a + n > h) {
+      free(vrow);
+      return -2;
+    }
+    for (int px = xlo; px <= xhi; px++)
+      for (int k2 = 0; k2 < c; k2++) {
+        float v = 0.0f;
+        for (int k = 0; k < n; k++) {
+          const uint8_t* p = src + (size_t)(a + k) * stride + (size_t)px * c;
+          const float al = (float)p[3] * inv255;
+          const float x = k2 < 3 ? (float)p[k2] * inv255 * al : al;
+          v = fmaf(cf[k], x, v);
+        }
+        vrow[px * c + k2] = v;
+      }
+    uint8_t* d = dst + (size_t)r * cw * c;
+    for (int x = 0; x < cw; x++) {
+      const int ox = cx + (flip ? cw - 1 - x : x);
+      const int xa = xfirst[ox], xn = xcount[ox];
+      const float* cfx = xw + (size_t)ox * xwidth;
+      float px4[4];
+      for (int k2 = 0; k2 < c; k2++) {
+        float hsum = 0.0f;
+        for (int k = 0; k < xn; k++) hsum = fmaf(cfx[k], vrow[(xa + k) * c + k2], hsum);
+        px4[k2] = hsum;
+      }
+      if (px4[3] >= 7.52316384526264e-37f) {
+        const float ia = 1.0f / px4[3];
+        for (int k2 = 0; k2 < 3; k2++) px4[k2] = px4[k2] * ia;
+      }
+      for (int k2 = 0; k2 < c; k2++) {
+        float f = px4[k2] * 255.0f;
+        f = f + 0.5f;
+        if (f < 0.0f) f = 0.0f;
+        if (f > 255.0f) f = 255.0f;
+        d[x * c + k2] = (uint8_t)f;
+      }
+    }
+  }
+  free(vrow);
+  return 0;
+}
