@@ -82,12 +82,15 @@ extern "C" {
  * Erasing behind the output form -- mxd_erase_mode, mxd_erase_elem, mxd_erase,
  * mxd_erase_validate, mxd_erase_apply, mxd_erase_normals,
  * mxd_resize_crop_batch_erase, mxd_resize_crop_to_device_erase,
- * mxd_jpeg_resize_crop_to_device_erase. */
+ * mxd_jpeg_resize_crop_to_device_erase.
+ * 7, added without a new number (test for MXD_HAS_WARP_CUBIC): the warp mode
+ * MXD_WARP_BICUBIC. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
 #define MXD_HAS_TONE 1
 #define MXD_HAS_WARP 1
+#define MXD_HAS_WARP_CUBIC 1
 #define MXD_HAS_ENHANCE 1
 #define MXD_HAS_MIX 1
 #define MXD_HAS_GAUSSIAN_BLUR 1
@@ -687,10 +690,24 @@ int mxd_jpeg_resize_crop_to_device_tone(const mxd_jpeg_image* images, const mxd_
  *     row yc, v2 the same on row Y + 1 if 0 <= Y + 1 < h, else v1; the result
  *     is (uint8) trunc(v1 + (v2 - v1) dy): truncation, where the rest of this
  *     library rounds.
+ *   BICUBIC (feature test: MXD_HAS_WARP_CUBIC): sx, sy and the test that
+ *     leaves the pixel unwritten are BILINEAR's, word for word; then
+ *     sx -= 0.5, sy -= 0.5, X = FLOOR(sx), Y = FLOOR(sy), dx = sx - X,
+ *     dy = sy - Y, X -= 1, Y -= 1; columns xk = clamp(X + k, 0, w - 1) for
+ *     k = 0 .. 3.  In double, nothing fused, CUB(v1, v2, v3, v4, d) is
+ *     p1 = v2, p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4,
+ *     p4 = -v1 + v2 - v3 + v4, p1 + d (p2 + d (p3 + d p4)).  Per channel
+ *     r1 = CUB(p[x0], p[x1], p[x2], p[x3], dx) on row clamp(Y, 0, h - 1); r2
+ *     the same on row Y + 1 if 0 <= Y + 1 < h, else r1; r3 on row Y + 2, else
+ *     r2; r4 on row Y + 3, else r3; v = CUB(r1, r2, r3, r4, dy); the byte is 0
+ *     if v <= 0, 255 if v >= 255, else (uint8) trunc(v).  This is the cubic
+ *     convolution with a = -1 of Pillow's transform, not the a = -0.5
+ *     Catmull-Rom of Pillow's resize (MXD_FILTER_CATMULLROM).
  *
  * In a call the stage order is geometry, warp, tone, colour, output form: the
  * tone statistics are those of the warped result, fill pixels included. */
-enum mxd_warp_mode { MXD_WARP_NONE = 0, MXD_WARP_NEAREST = 1, MXD_WARP_BILINEAR = 2 };
+/* (3 to 7 are not assigned) */
+enum mxd_warp_mode { MXD_WARP_NONE = 0, MXD_WARP_NEAREST = 1, MXD_WARP_BILINEAR = 2, MXD_WARP_BICUBIC = 8 };
 
 typedef struct mxd_warp {
   int32_t mode;    /* mxd_warp_mode; NONE: the image's bytes stay as they are, nothing else is read */

@@ -421,6 +421,11 @@ int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDe
   if (st.kind == StageKind::Warp) {
     what = "warp launch failed: ";
     rc = mxd::launch_warp(static_cast<const mxd::WarpRowDev*>(entries), st.count, st.blocks, st.pre_blocks, L.warp_tab, stream);
+    if (rc == 0 && L.warp_cubic_end > L.warp_cubic_begin) {
+      what = "cubic warp launch failed: ";
+      rc = mxd::launch_warp_cubic(static_cast<const mxd::WarpRowDev*>(entries), st.count, L.warp_cubic_begin,
+                                  L.warp_cubic_end, stream);
+    }
   } else if (st.kind == StageKind::Enhance) {
     what = "enhance launch failed: ";
     rc = mxd::launch_enhance(static_cast<const mxd::EnhanceRowDev*>(entries), st.count, st.blocks, stream);

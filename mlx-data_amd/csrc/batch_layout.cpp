@@ -397,7 +397,13 @@ void fill_warps(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
     e.path = wp.mode == MXD_WARP_NONE       ? mxd::kWarpCopy
              : warp_tabled(wp)              ? mxd::kWarpTable
              : wp.mode == MXD_WARP_NEAREST  ? mxd::kWarpFixed
+             : wp.mode == MXD_WARP_BICUBIC  ? mxd::kWarpCubic
                                             : mxd::kWarpBilinear;
+    if (e.path == mxd::kWarpCubic) {
+      // warp_cubic_rows' tiles: from the first cubic image's first to the last one's last
+      if (L.warp_cubic_end == 0) L.warp_cubic_begin = e.tile_begin;
+      L.warp_cubic_end = st.blocks;
+    }
     e.fill = (uint32_t)wp.fill[0] | (uint32_t)wp.fill[1] << 8 | (uint32_t)wp.fill[2] << 16;
     e.tab_off = 0, e.tab_index = -1;
     if (e.path == mxd::kWarpTable) {

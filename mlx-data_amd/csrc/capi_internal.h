@@ -402,6 +402,9 @@ struct BatchLayout {
   size_t scratch_bytes = 0, b_at = 0, warp_tab_at = 0, tone_ws_at = 0, tone_stat_bytes = 0;
   uint8_t* warp_tab = nullptr;
   uint8_t* tone_ws = nullptr;
+  // The warp stage's tiles [warp_cubic_begin, warp_cubic_end) hold every
+  // bicubic image's (warp_cubic.hip's launch); both 0 without one.
+  int32_t warp_cubic_begin = 0, warp_cubic_end = 0;
   // The chain by its members' names (0 / false for a stage the call has not).
   bool warped() const { return stage(StageKind::Warp) != nullptr; }
   bool enhanced() const { return stage(StageKind::Enhance) != nullptr; }

@@ -92,5 +92,15 @@ __device__ __forceinline__ int src_records(int shift, int rows, int stride, int 
   return (shift + (rows - 1) * stride + (row_bytes < stride ? row_bytes : stride) + 3) & ~3;
 }
 
+// The three bytes of the pixel at byte offset o (0 <= o <= limit - 3) of an
+// image whose rows take `limit` bytes (a multiple of 16, >= 16) from base: one
+// 8-byte load at a 4-byte aligned address clamped to end inside those bytes.
+__device__ __forceinline__ uint32_t fetch_rgb(const uint8_t* base, int64_t limit, int64_t o) {
+  const int64_t a = min(o & ~(int64_t)3, limit - 8);
+  const uint32_t* p = reinterpret_cast<const uint32_t*>(base + a);
+  const uint64_t v = (uint64_t)p[0] | (uint64_t)p[1] << 32;
+  return (uint32_t)(v >> (8 * (int)(o - a))) & 0xffffffu;
+}
+
 }  // namespace dev
 }  // namespace mxd

@@ -1148,10 +1148,14 @@ std::shared_ptr<Array> ImageTone::apply_image(const std::shared_ptr<Array>& img)
 int32_t parse_resample(const std::string& op, const std::string& name) {
   if (name == "nearest") return MXD_WARP_NEAREST;
   if (name == "bilinear") return MXD_WARP_BILINEAR;
-  throw std::invalid_argument(op + ": unknown resample '" + name + "' (one of nearest, bilinear)");
+  // ("bicubic" names two kernels in Pillow: this one, a = -1, is not the resize filter "catmullrom")
+  if (name == "cubic") return MXD_WARP_BICUBIC;
+  throw std::invalid_argument(op + ": unknown resample '" + name + "' (one of nearest, bilinear, cubic)");
 }
 
-const char* resample_name(int32_t mode) { return mode == MXD_WARP_BILINEAR ? "bilinear" : "nearest"; }
+const char* resample_name(int32_t mode) {
+  return mode == MXD_WARP_BICUBIC ? "cubic" : mode == MXD_WARP_BILINEAR ? "bilinear" : "nearest";
+}
 
 std::array<double, 6> affine_rotate_matrix(int64_t w, int64_t h, double angle) {
   // Image.rotate, operation for operation (volatile: every product and sum

@@ -460,7 +460,7 @@ class ImageAffine : public ImageOp {
   int32_t mode_;
   std::array<uint8_t, 4> fill_{{0, 0, 0, 0}};
 };
-// "nearest" / "bilinear" -> mxd_warp_mode (std::invalid_argument otherwise) and back.
+// "nearest" / "bilinear" / "cubic" -> mxd_warp_mode (std::invalid_argument otherwise) and back.
 int32_t parse_resample(const std::string& op, const std::string& name);
 const char* resample_name(int32_t mode);
 // Pillow's Image.rotate matrix for expand=False about (w / 2, h / 2).

@@ -242,8 +242,10 @@ inline bool tone_needs_stats(int op) { return op >= 3; }
 // kWarpTable, launched only when there is one) first writes the index tables
 // xt[w], yt[h] (int32) at tab_off in the workspace.
 constexpr int kWarpTileW = 64, kWarpTileH = 16;
-// An image's code path: its bytes copied, 16.16 fixed point, double bilinear, table lookup.
-enum WarpPath : int32_t { kWarpCopy = 0, kWarpFixed = 1, kWarpBilinear = 2, kWarpTable = 3 };
+// An image's code path: its bytes copied, 16.16 fixed point, double bilinear,
+// table lookup -- warp_rows' four -- or the double bicubic, which is
+// warp_cubic_rows' (warp_cubic.hip): each kernel leaves the other's images alone.
+enum WarpPath : int32_t { kWarpCopy = 0, kWarpFixed = 1, kWarpBilinear = 2, kWarpTable = 3, kWarpCubic = 4 };
 struct WarpRowDev {
   const uint8_t* src;  // u8 rows (16-byte aligned base, stride a multiple of 16)
   uint8_t* dst;        // scratch rows like src, or the caller's u8 destination (any alignment)
@@ -260,6 +262,9 @@ struct WarpRowDev {
 static_assert(sizeof(WarpRowDev) == 112, "WarpRowDev layout");
 // tab_rows: how many entries take the table path; ws: the tables' workspace.
 int launch_warp(const WarpRowDev* rows, int nimgs, int ntiles, int tab_rows, uint8_t* ws, void* stream);
+// warp_cubic_rows over the tiles [tile_first, tile_end) of the same entries:
+// from the first kWarpCubic image's first tile to the last one's last.
+int launch_warp_cubic(const WarpRowDev* rows, int nimgs, int tile_first, int tile_end, void* stream);
 // The enhance stage (enhance.hip): behind the resize launches (and the warp
 // stage) and before the second pass of an enhance call (mxd_enhance), over u8
 // RGB scratch rows.  One entry per image; a workgroup takes one kEnhTileW x

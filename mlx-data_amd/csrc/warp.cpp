@@ -16,7 +16,8 @@ int warp_check(const mxd_warp& wp, int32_t w, int32_t h, int32_t i) {
   auto at = [i](const std::string& msg) {
     return fail(MXD_ERR_INVALID, "mxd_warp: " + msg + " (image " + std::to_string(i) + ")");
   };
-  if (wp.mode < MXD_WARP_NONE || wp.mode > MXD_WARP_BILINEAR) return at("unknown mode " + std::to_string(wp.mode));
+  if ((wp.mode < MXD_WARP_NONE || wp.mode > MXD_WARP_BILINEAR) && wp.mode != MXD_WARP_BICUBIC)
+    return at("unknown mode " + std::to_string(wp.mode));
   if (wp.mode == MXD_WARP_NONE) return MXD_OK;
   for (int k = 0; k < 6; k++)
     if (!std::isfinite(wp.m[k])) return at("m[" + std::to_string(k) + "] is not finite");
@@ -36,6 +37,25 @@ int warp_check(const mxd_warp& wp, int32_t w, int32_t h, int32_t i) {
 inline int floor_i(double v) { return v < 0.0 ? (int)std::floor(v) : (int)v; }
 inline int coord_i(double v) { return v < 0.0 ? -1 : (int)v; }
 inline int clamp_i(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// Pillow's BICUBIC macro: the cubic convolution with a = -1, every operation rounded.
+inline double cub(double v1, double v2, double v3, double v4, double d) {
+  volatile double p2 = -v1 + v3;
+  volatile double a0 = v1 - v2;
+  volatile double a1 = 2.0 * a0;
+  volatile double a2 = a1 + v3;
+  volatile double p3 = a2 - v4;
+  volatile double b0 = -v1 + v2;
+  volatile double b1 = b0 - v3;
+  volatile double p4 = b1 + v4;
+  volatile double t0 = d * p4;
+  volatile double t1 = p3 + t0;
+  volatile double t2 = d * t1;
+  volatile double t3 = p2 + t2;
+  volatile double t4 = d * t3;
+  volatile double r = v2 + t4;
+  return r;
+}
 
 }  // namespace
 
@@ -118,6 +138,41 @@ extern "C" int mxd_warp_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, int64
       for (int x = 0; x < w; x++) {
         const int64_t xin = (a2 + a1 * y + a0 * x) >> 16, yin = (a5 + a4 * y + a3 * x) >> 16;
         if (xin >= 0 && xin < w && yin >= 0 && yin < h) std::memcpy(dst(y, x), src((int)yin, (int)xin), 3);
+      }
+    return MXD_OK;
+  }
+  if (warp->mode == MXD_WARP_BICUBIC) {
+    // the source position and the outside test are BILINEAR's (below); 4 x 4 taps, rows first
+    for (int y = 0; y < h; y++)
+      for (int x = 0; x < w; x++) {
+        volatile double t0 = a[0] * (x + 0.5), t1 = a[1] * (y + 0.5);
+        volatile double t2 = t0 + t1;
+        double sx = t2 + a[2];
+        volatile double u0 = a[3] * (x + 0.5), u1 = a[4] * (y + 0.5);
+        volatile double u2 = u0 + u1;
+        double sy = u2 + a[5];
+        if (sx < 0.0 || sx >= (double)w || sy < 0.0 || sy >= (double)h) continue;
+        sx -= 0.5;
+        sy -= 0.5;
+        int X = floor_i(sx), Y = floor_i(sy);
+        const double dx = sx - X, dy = sy - Y;
+        X -= 1, Y -= 1;
+        int xk[4];
+        for (int k = 0; k < 4; k++) xk[k] = clamp_i(X + k, 0, w - 1);
+        for (int c = 0; c < 3; c++) {
+          double r[4];
+          for (int k = 0; k < 4; k++) {
+            const bool have = k == 0 || (Y + k >= 0 && Y + k < h);
+            if (!have) {
+              r[k] = r[k - 1];
+              continue;
+            }
+            const int yy = k == 0 ? clamp_i(Y, 0, h - 1) : Y + k;
+            r[k] = cub(src(yy, xk[0])[c], src(yy, xk[1])[c], src(yy, xk[2])[c], src(yy, xk[3])[c], dx);
+          }
+          const double v = cub(r[0], r[1], r[2], r[3], dy);
+          dst(y, x)[c] = v <= 0.0 ? 0 : v >= 255.0 ? 255 : (uint8_t)(int)v;
+        }
       }
     return MXD_OK;
   }

@@ -14,8 +14,10 @@
 //            image's entry is read through a uniform (scalar) address and its
 //            code path chosen by a uniform branch: a copy (MXD_WARP_NONE), the
 //            table lookup, 16.16 fixed point in 64-bit integers, or the double
-//            bilinear.  Every source pixel is fetched with one 8-byte load at a
-//            4-byte aligned address clamped to end inside the image's own
+//            bilinear; a bicubic image's workgroups return at once (its
+//            tiles are warp_cubic.hip's).  Every source pixel is fetched
+//            with one 8-byte load at a 4-byte aligned address (devutil.h's
+//            fetch_rgb) clamped to end inside the image's own
 //            rows (16-byte aligned base, stride a multiple of 16, so
 //            stride * h bytes are the image's); indices are clamped or
 //            rejected before the address is formed, and a rejected pixel takes
@@ -40,14 +42,7 @@ static_assert(kGroups * kWarpTileH == kThreads, "a lane per four pixels of the t
 
 using WarpRowK = const __attribute__((address_space(4))) WarpRowDev;
 
-// The three bytes of the pixel at byte offset o (0 <= o <= limit - 3) of an
-// image whose rows take `limit` bytes (a multiple of 16, >= 16) from base.
-__device__ __forceinline__ uint32_t fetch(const uint8_t* base, int64_t limit, int64_t o) {
-  const int64_t a = min(o & ~(int64_t)3, limit - 8);
-  const uint32_t* p = reinterpret_cast<const uint32_t*>(base + a);
-  const uint64_t v = (uint64_t)p[0] | (uint64_t)p[1] << 32;
-  return (uint32_t)(v >> (8 * (int)(o - a))) & 0xffffffu;
-}
+using dev::fetch_rgb;  // every source pixel's load (devutil.h)
 
 __device__ __forceinline__ int64_t fix16(double v) {
   const double t = v * 65536.0 + 0.5;
@@ -106,10 +101,11 @@ __global__ __launch_bounds__(kThreads) void warp_rows(const void* __restrict__ r
   const uint32_t fill = e.fill;
   uint32_t px[4] = {fill, fill, fill, fill};
   const int path = e.path;
+  if (path == kWarpCubic) return;  // warp_cubic_rows' image (warp_cubic.hip)
   if (path == kWarpCopy) {
 #pragma unroll
     for (int k = 0; k < 4; k++)
-      if (k < cnt) px[k] = fetch(src, limit, (int64_t)y * sstride + 3 * (x0 + k));
+      if (k < cnt) px[k] = fetch_rgb(src, limit, (int64_t)y * sstride + 3 * (x0 + k));
   } else if (path == kWarpTable) {
     const int32_t* const xt = reinterpret_cast<const int32_t*>(ws + e.tab_off);
     const int yin = xt[w + y];
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void warp_rows(const void* __restrict__ r
       for (int k = 0; k < 4; k++) {
         if (k >= cnt) continue;
         const int xin = xt[x0 + k];
-        if (xin >= 0 && xin < w) px[k] = fetch(src, limit, (int64_t)yin * sstride + 3 * xin);
+        if (xin >= 0 && xin < w) px[k] = fetch_rgb(src, limit, (int64_t)yin * sstride + 3 * xin);
       }
     }
   } else if (path == kWarpFixed) {
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void warp_rows(const void* __restrict__ r
     for (int k = 0; k < 4; k++) {
       if (k >= cnt) continue;
       const int64_t xin = (bx + a0 * (x0 + k)) >> 16, yin = (by + a3 * (x0 + k)) >> 16;
-      if (xin >= 0 && xin < w && yin >= 0 && yin < h) px[k] = fetch(src, limit, yin * sstride + 3 * xin);
+      if (xin >= 0 && xin < w && yin >= 0 && yin < h) px[k] = fetch_rgb(src, limit, yin * sstride + 3 * xin);
     }
   } else {
     const double m0 = e.m[0], m2 = e.m[2], m3 = e.m[3], m5 = e.m[5];
@@ -151,12 +147,12 @@ __global__ __launch_bounds__(kThreads) void warp_rows(const void* __restrict__ r
       const int X = (int)fx, Y = (int)fy;
       const double dx = sx - fx, dy = sy - fy;
       const int xa = min(max(X, 0), w - 1), xb = min(max(X + 1, 0), w - 1), yc = min(max(Y, 0), h - 1);
-      const uint32_t p00 = fetch(src, limit, (int64_t)yc * sstride + 3 * xa);
-      const uint32_t p01 = fetch(src, limit, (int64_t)yc * sstride + 3 * xb);
+      const uint32_t p00 = fetch_rgb(src, limit, (int64_t)yc * sstride + 3 * xa);
+      const uint32_t p01 = fetch_rgb(src, limit, (int64_t)yc * sstride + 3 * xb);
       const bool below = Y + 1 >= 0 && Y + 1 < h;
       const int yb = below ? Y + 1 : yc;  // (a row of the image either way; not used unless below)
-      const uint32_t p10 = fetch(src, limit, (int64_t)yb * sstride + 3 * xa);
-      const uint32_t p11 = fetch(src, limit, (int64_t)yb * sstride + 3 * xb);
+      const uint32_t p10 = fetch_rgb(src, limit, (int64_t)yb * sstride + 3 * xa);
+      const uint32_t p11 = fetch_rgb(src, limit, (int64_t)yb * sstride + 3 * xb);
       uint32_t o = 0;
 #pragma unroll
       for (int c = 0; c < 3; c++) {

@@ -416,6 +416,7 @@ def jpeg_resize_crop_to_device_tone(images, tones, colors, n, out_dtype=MXD_U8, 
 MXD_WARP_NONE = 0
 MXD_WARP_NEAREST = 1
 MXD_WARP_BILINEAR = 2
+MXD_WARP_BICUBIC = 8
 
 
 class MxdWarp(ctypes.Structure):

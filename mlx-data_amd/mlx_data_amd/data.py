@@ -102,7 +102,8 @@ fifth addition): ``image_affine(key, matrix)`` (six numbers, Pillow's AFFINE
 data: output pixel -> source position), ``image_shear(key, x=0.0, y=0.0)``,
 ``image_translate(key, x=0.0, y=0.0)`` (pixels; the content moves by -t, as in
 timm) and ``image_affine_rotate(key, angle)`` (degrees, Pillow's sign, about
-the centre, same size), each with ``resample="nearest" | "bilinear"``,
+the centre, same size), each with ``resample="nearest" | "bilinear" | "cubic"``
+(``"cubic"``: Pillow's ``Image.BICUBIC`` in ``transform`` / ``rotate``, a = -1),
 ``fill=0`` (a scalar or ``(r, g, b)`` in 0..255) and ``output_key=""``, and
 the random forms ``image_random_shear(key, x=None, y=None)``,
 ``image_random_translate(key, x=None, y=None)`` and

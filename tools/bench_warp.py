@@ -18,6 +18,12 @@ process for --rounds rounds (3 rounds: 9 windows each):
   d       what a user runs today: the u8 mxd_resize_crop_batch, then torch on
           the same stream -- affine_grid, grid_sample (bilinear, zeros), / 255,
           normalise, cast to bfloat16 (the result is CHW already)
+  q, q2   as b with MXD_WARP_BICUBIC (warp_cubic.hip; twice, for its own spread)
+  g       as q through the diagnostic build with warp_cubic.hip's LDS route off
+          (make -C mlx-data_amd cubic_gather), loaded beside the product build
+          as tools/lib_ab.py loads its variants; its output must equal q's
+  e       as d with grid_sample(mode="bicubic"): another kernel (a = -0.75) and
+          other bytes, the route a bicubic policy has without the mode
 
 --variants picks a subset (a profiler run of the warp call alone: --variants b).
 
@@ -79,6 +85,7 @@ def run_workload(name, capi, torch, rounds, emit, only):
     bilinear = capi.make_warps([(capi.MXD_WARP_BILINEAR, FILL, rot)] * B)
     nearest = capi.make_warps([(capi.MXD_WARP_NEAREST, FILL, rot)] * B)
     table = capi.make_warps([(capi.MXD_WARP_NEAREST, FILL, (1.0, 0.0, 20.5, 0.0, 1.0, -12.25))] * B)
+    cubic = capi.make_warps([(capi.MXD_WARP_BICUBIC, FILL, rot)] * B)
     # the same rotation in affine_grid's normalised coordinates (square images: no aspect term)
     r = math.radians(30.0)
     theta = torch.tensor([[math.cos(r), math.sin(r), 0.0], [-math.sin(r), math.cos(r), 0.0]], device="cuda:0")
@@ -93,23 +100,37 @@ def run_workload(name, capi, torch, rounds, emit, only):
     def a(i):
         call(L.mxd_resize_crop_batch_fmt(arrays["chw16"][i % 2], B, ctypes.byref(fmt), dev, hs))
 
-    def warp_call(warps):
+    def warp_call(warps, lib=L):
         def f(i):
-            call(L.mxd_resize_crop_batch_warp(arrays["chw16"][i % 2], warps, None, None, B, capi.MXD_U8, ctypes.byref(fmt),
-                                              dev, hs))
+            if lib.mxd_resize_crop_batch_warp(arrays["chw16"][i % 2], warps, None, None, B, capi.MXD_U8, ctypes.byref(fmt),
+                                              dev, hs) != 0:
+                raise RuntimeError(lib.mxd_last_error().decode())
         return f
 
-    def d(i):
-        call(L.mxd_resize_crop_batch(arrays["u8"][i % 2], B, capi.MXD_U8, dev, hs))
-        with torch.cuda.stream(ext):
-            x = u8s[i % 2].permute(0, 3, 1, 2).float()
-            grid = F.affine_grid(theta, (B, C, ch, cw), align_corners=False)
-            y = F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
-            ((y / 255 - mean_t) / std_t).to(torch.bfloat16)
+    def torch_route(mode):
+        def f(i):
+            call(L.mxd_resize_crop_batch(arrays["u8"][i % 2], B, capi.MXD_U8, dev, hs))
+            with torch.cuda.stream(ext):
+                x = u8s[i % 2].permute(0, 3, 1, 2).float()
+                grid = F.affine_grid(theta, (B, C, ch, cw), align_corners=False)
+                y = F.grid_sample(x, grid, mode=mode, padding_mode="zeros", align_corners=False)
+                ((y / 255 - mean_t) / std_t).to(torch.bfloat16)
+        return f
 
-    every = {"a": a, "b": warp_call(bilinear), "c": warp_call(nearest), "t": warp_call(table), "d": d, "a2": a}
+    every = {"a": a, "b": warp_call(bilinear), "c": warp_call(nearest), "t": warp_call(table), "d": torch_route("bilinear"),
+             "q": warp_call(cubic), "e": torch_route("bicubic"), "a2": a, "q2": warp_call(cubic)}
+    if not only or "g" in only:
+        every["g"] = warp_call(cubic, gather_lib())
     variants = {k: f for k, f in every.items() if not only or k in only}
     try:
+        if "q" in variants and "g" in variants:  # both routes give the same bytes
+            variants["q"](0)
+            stream.synchronize()
+            ref = outs[0].view(torch.int16).cpu()
+            outs[0].zero_()
+            variants["g"](0)
+            stream.synchronize()
+            assert torch.equal(outs[0].view(torch.int16).cpu(), ref), "the gather build's output differs"
         for f in variants.values():  # every shape and variant warmed first
             for i in range(10):
                 f(i)
@@ -123,18 +144,36 @@ def run_workload(name, capi, torch, rounds, emit, only):
             med[k] = statistics.median(w)
             emit({"workload": name, "variant": k, "images": B, "ms_per_launch": round(med[k], 5), "min": min(w),
                   "max": max(w), "windows": w})
-        if not only:
-            lo = min(med["a"], med["a2"])
-            emit({"workload": name, "summary": True, "b_over_a": round(med["b"] / lo, 4), "c_over_a": round(med["c"] / lo, 4),
-                  "t_over_a": round(med["t"] / lo, 4), "b_over_d": round(med["b"] / med["d"], 4),
-                  "c_over_d": round(med["c"] / med["d"], 4), "d_over_b": round(med["d"] / med["b"], 2),
-                  "d_over_c": round(med["d"] / med["c"], 2), "a_spread": round(abs(med["a"] - med["a2"]) / lo, 4)})
+        def ratio(x, y):
+            return round(med[x] / med[y], 4) if x in med and y in med else None
+
+        summary = {"workload": name, "summary": True}
+        if "a" in med and "a2" in med:
+            med["lo"] = min(med["a"], med["a2"])
+            summary["a_spread"] = round(abs(med["a"] - med["a2"]) / med["lo"], 4)
+        if "q" in med and "q2" in med:
+            summary["q_spread"] = round(abs(med["q"] - med["q2"]) / min(med["q"], med["q2"]), 4)
+        for x, y in (("b", "lo"), ("c", "lo"), ("t", "lo"), ("q", "lo"), ("b", "d"), ("c", "d"), ("d", "b"), ("d", "c"),
+                     ("q", "b"), ("e", "q"), ("g", "q")):
+            if ratio(x, y) is not None:
+                summary[f"{x}_over_{'a' if y == 'lo' else y}"] = ratio(x, y)
+        emit(summary)
     finally:
         stream.synchronize()
         for src, dst, _, _ in sets:
             src.free()
             dst.free()
         stream.close()
+
+
+def gather_lib():
+    """The diagnostic build beside the product library (tools/lib_ab.py's way)."""
+    path = os.path.join(REPO, "tools", "libmxd_amd_var_cubic_gather.so")
+    G = ctypes.CDLL(path, mode=os.RTLD_LOCAL | os.RTLD_NOW)
+    G.mxd_last_error.restype = ctypes.c_char_p
+    if G.mxd_set_device(0) != 0:
+        raise RuntimeError("cubic_gather: mxd_set_device failed")
+    return G
 
 
 def main():
