@@ -78,6 +78,9 @@ extern "C" {
  * mxd_resize_crop_to_device_mix, mxd_jpeg_resize_crop_to_device_mix.
  * 7, added without a new number (test for MXD_HAS_GAUSSIAN_BLUR / the
  * symbols): the enhance op MXD_ENHANCE_GAUSSIAN_BLUR and mxd_gaussian_weights.
+ * 7, added without a new number (test for MXD_HAS_PIL_BLUR / the symbols): the
+ * enhance ops MXD_ENHANCE_PIL_GAUSSIAN_BLUR and MXD_ENHANCE_PIL_BOX_BLUR and
+ * mxd_pil_blur_params.
  * 7, added without a new number (test for MXD_HAS_ERASE / the symbols): Random
  * Erasing behind the output form -- mxd_erase_mode, mxd_erase_elem, mxd_erase,
  * mxd_erase_validate, mxd_erase_apply, mxd_erase_normals,
@@ -94,6 +97,7 @@ extern "C" {
 #define MXD_HAS_ENHANCE 1
 #define MXD_HAS_MIX 1
 #define MXD_HAS_GAUSSIAN_BLUR 1
+#define MXD_HAS_PIL_BLUR 1
 #define MXD_HAS_ERASE 1
 
 enum mxd_status {
@@ -775,9 +779,13 @@ int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_
  * between: MXD_TONE_CONTRAST's rule.  Factor 1 returns q, factor 0 returns D.
  *
  * GAUSSIAN_BLUR is not a blend.  It is a true separable Gaussian with
- * torchvision's kernel and padding (transforms.GaussianBlur, the blur of the
- * SimCLR / BYOL / MoCo v3 / DINO recipes) -- not Pillow's box-blur
- * approximation of ImageFilter.GaussianBlur.  factor is sigma, reserved[0] the
+ * torchvision's kernel and padding (transforms.GaussianBlur on a tensor or a
+ * PIL image: the blur of SimCLR, BYOL and the loaders written with
+ * torchvision's transform) -- not Pillow's box-blur approximation of
+ * ImageFilter.GaussianBlur, which is PIL_GAUSSIAN_BLUR below: the blur of the
+ * loaders that call ImageFilter.GaussianBlur on a PIL image (MoCo v2 / v3,
+ * DINO, Barlow Twins, VICReg, DeiT III's 3-Augment).  The two differ in most
+ * bytes.  factor is sigma, reserved[0] the
  * kernel size k (odd, 3..33), R = (k - 1) / 2.  The weights are
  * mxd_gaussian_weights' (below).  Padding is torch / NumPy "reflect": the
  * mirror without repeating the edge, repeated for any radius with period
@@ -792,6 +800,31 @@ int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_
  * and the result is rint(a) (half to even) clamped to 0..255.  The symmetric
  * form makes the blur of a mirrored image the mirror of the blur, bit for bit.
  *
+ * PIL_GAUSSIAN_BLUR and PIL_BOX_BLUR are Pillow's ImageFilter.GaussianBlur(r)
+ * and ImageFilter.BoxBlur(r), bit for bit; factor is r, reserved is 0.  Both
+ * are passes of Pillow's extended box blur in 8.24 fixed point.  One
+ * horizontal pass with the box radius fr (a float32) over a row of w bytes of
+ * one channel is, with every operation of ww a float32 operation and the rest
+ * in uint32 (which never wraps),
+ *
+ *   R  = (int)fr
+ *   ww = (uint32)((float)(1 << 24) / (fr * 2 + 1))
+ *   fw = ((1 << 24) - (2 R + 1) ww) / 2
+ *   out[x] = (ww sum_{d=-R..R} in[c(x+d)] + fw (in[c(x-R-1)] + in[c(x+R+1)])
+ *             + (1 << 23)) >> 24,          c(i) = min(max(i, 0), w - 1)
+ *
+ * and a vertical pass is the same over a column.  PIL_BOX_BLUR is fr = r: one
+ * pass over every row, then one over every column of the result.
+ * PIL_GAUSSIAN_BLUR is three passes over the rows, then three over the
+ * columns, each on the bytes the one before it wrote, with fr from r in
+ * float32 except the square root, which is a double's: s2 = r r / 3,
+ * L = (float)sqrt(12.0 s2 + 1.0), l = floor((L - 1) / 2),
+ * a = (2 l + 1) (l (l + 1) - 3 s2), a /= 6 (s2 - (l + 1)^2), fr = l + a.
+ * fr == 0 (r == 0) leaves the bytes as they are.  The arithmetic is integer,
+ * so the order of the sums is free; the rounding to bytes after every pass is
+ * not.  A pass is symmetric, so these blurs commute with the mirror too.
+ * mxd_pil_blur_params (below) gives fr, ww, fw and the pass count.
+ *
  * In a call the stage order is geometry, warp, enhance, tone, colour, output
  * form: the tone statistics are those of the enhanced bytes. */
 enum mxd_enhance_op {
@@ -800,12 +833,15 @@ enum mxd_enhance_op {
   MXD_ENHANCE_COLOR = 2,
   MXD_ENHANCE_BRIGHTNESS = 3,
   /* (4 to 7 are not assigned) */
-  MXD_ENHANCE_GAUSSIAN_BLUR = 8
+  MXD_ENHANCE_GAUSSIAN_BLUR = 8,
+  MXD_ENHANCE_PIL_GAUSSIAN_BLUR = 9,
+  MXD_ENHANCE_PIL_BOX_BLUR = 10
 };
 
 typedef struct mxd_enhance {
   int32_t op;          /* mxd_enhance_op; NONE: the image's bytes stay as they are, factor is not read */
-  float factor;        /* f: finite, 0 <= f <= 1e6; GAUSSIAN_BLUR: sigma, finite, 0 < sigma <= 1e6 */
+  float factor;        /* f: finite, 0 <= f <= 1e6; GAUSSIAN_BLUR: sigma, finite, 0 < sigma <= 1e6;
+                          PIL_GAUSSIAN_BLUR, PIL_BOX_BLUR: Pillow's radius, finite, >= 0, (int)fr + 1 <= 16 */
   int32_t reserved[2]; /* must be 0; GAUSSIAN_BLUR: reserved[0] is the kernel size k (odd, 3..33), reserved[1] 0 */
 } mxd_enhance;
 
@@ -832,6 +868,14 @@ int mxd_gaussian_weights(float sigma, int32_t k, float* out);
  * source rows per step (4 or 8); 0 = the measured default.  The result bytes
  * do not depend on it.  MXD_ERR_INVALID for anything else. */
 int mxd_blur_shape(int32_t seg_rows, int32_t step);
+/* Host only: what MXD_ENHANCE_PIL_GAUSSIAN_BLUR or MXD_ENHANCE_PIL_BOX_BLUR
+ * (op) makes of the radius, as the device takes it: the box radius *fr, the
+ * weights *ww and *fw of one pass and the number of passes per axis (3 or 1);
+ * fr == 0 means the bytes stay as they are (ww and fw are then not used).
+ * Any of the four pointers may be null.  MXD_ERR_INVALID for another op, a
+ * radius that is not finite or is negative, or one whose (int)fr + 1 exceeds
+ * 16 (a Gaussian radius above about 16.4, a box radius of 16 or more). */
+int mxd_pil_blur_params(int32_t op, float radius, float* fr, uint32_t* ww, uint32_t* fw, int32_t* passes);
 
 /* The _warp calls with enhances[i] applied to images[i]'s result after
  * warps[i] and before tones[i].  warps, tones, colors and fmt may each be
@@ -841,7 +885,8 @@ int mxd_blur_shape(int32_t seg_rows, int32_t step);
  * channels != 3; everything is validated before any launch.  Every image is
  * resized as a u8 image into a scratch by the kernels of the plain calls; one
  * more launch on the same stream (enhance_rows; blur_rows for the images whose
- * op is GAUSSIAN_BLUR) reads those rows, or the warp
+ * op is GAUSSIAN_BLUR, pilblur_rows for PIL_GAUSSIAN_BLUR and PIL_BOX_BLUR)
+ * reads those rows, or the warp
  * stage's, and writes the destinations when nothing follows, else the other
  * of the two scratches, which the row stage of the _tone calls reads. */
 int mxd_resize_crop_batch_enhance(const mxd_image* images, const mxd_warp* warps, const mxd_enhance* enhances,

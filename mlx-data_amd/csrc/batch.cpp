@@ -436,6 +436,12 @@ int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDe
                             reinterpret_cast<const mxd::BlurRecDev*>(dev + L.blur_at), L.blur_count, L.blur_units,
                             step > 0 ? step : kBlurStep, stream);
     }
+    if (rc == 0 && L.pilblur_count > 0) {
+      what = "pil blur launch failed: ";
+      rc = mxd::launch_pilblur(static_cast<const mxd::EnhanceRowDev*>(entries),
+                               reinterpret_cast<const mxd::PilBlurRecDev*>(dev + L.pilblur_at), L.pilblur_count,
+                               L.pilblur_units, stream);
+    }
   } else if (st.kind == StageKind::Mix) {
     what = "mix launch failed: ";
     rc = mxd::launch_mix(static_cast<const mxd::MixRowDev*>(entries), st.count, st.blocks, ofd, stream);

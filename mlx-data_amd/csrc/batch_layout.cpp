@@ -430,10 +430,15 @@ void fill_enhances(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
     // takes the last entry with tile_begin <= its workgroup, so an entry
     // without tiles -- it begins where the next one does, or at the launch's
     // end -- is never chosen.
-    if (en.op != MXD_ENHANCE_GAUSSIAN_BLUR) st.blocks += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
-    e.op = en.op;
+    // A Pillow blur is pilblur_rows' (append_pilblurs) by the same rule, unless
+    // its box radius is 0: that one leaves the bytes as they are, like NONE.
+    const bool pil = pil_blur_op(en.op);
+    const bool copies = pil && pil_blur_params(en.op, en.factor).fr == 0.0f;
+    if (en.op != MXD_ENHANCE_GAUSSIAN_BLUR && (!pil || copies))
+      st.blocks += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
+    e.op = copies ? (int32_t)MXD_ENHANCE_NONE : en.op;
     // (MXD_ENHANCE_NONE reads no factor: zero, so equal calls make equal bytes)
-    e.factor = en.op == MXD_ENHANCE_NONE ? 0.0f : en.factor;
+    e.factor = e.op == MXD_ENHANCE_NONE ? 0.0f : en.factor;
   }
 }
 
@@ -467,6 +472,36 @@ void append_blurs(Batch& b, const PostOps& ops) {
   L.blur_count = (int32_t)recs.size();
   L.descs.resize(L.blur_at + (recs.size() * sizeof(mxd::BlurRecDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
   std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.blur_at), recs.data(), recs.size() * sizeof(mxd::BlurRecDev));
+}
+
+// The Pillow blur table, behind the blur table and only when some image has
+// one of the two ops with a box radius above 0: one record per such image, in
+// batch order.  The radius travels as R, ww and fw, part of the upload's bytes.
+void append_pilblurs(Batch& b, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  std::vector<mxd::PilBlurRecDev> recs;
+  for (int32_t i = 0; i < b.n; i++) {
+    const mxd_enhance& en = ops.enhances[i];
+    if (!pil_blur_op(en.op)) continue;
+    const PilBlurParams p = pil_blur_params(en.op, en.factor);
+    if (p.fr == 0.0f) continue;
+    const mxd_image& im = L.images[i];
+    mxd::PilBlurRecDev r{};
+    r.entry = i;
+    r.unit_begin = L.pilblur_units;
+    r.strips = (im.crop_w + mxd::kBlurStripW - 1) / mxd::kBlurStripW;
+    r.seg_rows = kPilBlurSegRows;
+    r.R = (int32_t)p.fr;
+    r.ww = p.ww, r.fw = p.fw;
+    r.passes = p.passes;
+    L.pilblur_units += r.strips * ((im.crop_h + r.seg_rows - 1) / r.seg_rows);
+    recs.push_back(r);
+  }
+  if (recs.empty()) return;
+  L.pilblur_at = L.descs.size();
+  L.pilblur_count = (int32_t)recs.size();
+  L.descs.resize(L.pilblur_at + (recs.size() * sizeof(mxd::PilBlurRecDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+  std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.pilblur_at), recs.data(), recs.size() * sizeof(mxd::PilBlurRecDev));
 }
 
 // The erase table, behind everything else of the upload and only when some
@@ -623,6 +658,7 @@ void append_stages(Batch& b, const mxd_image* callers, const PostOps& ops) {
     if (kind == StageKind::Mix) fill_mixes(b, *st, ops);
   }
   if (ops.enhances) append_blurs(b, ops);
+  if (ops.enhances) append_pilblurs(b, ops);
 }
 
 }  // namespace

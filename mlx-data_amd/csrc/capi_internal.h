@@ -417,6 +417,10 @@ struct BatchLayout {
   // every stage's entries, for blur_units workgroups; none without a blurred image.
   size_t blur_at = 0;
   int32_t blur_count = 0, blur_units = 0;
+  // The Pillow blur table (pilblur.hip), likewise: behind the blur table, for
+  // the images whose op is PIL_GAUSSIAN_BLUR or PIL_BOX_BLUR.
+  size_t pilblur_at = 0;
+  int32_t pilblur_count = 0, pilblur_units = 0;
   // The erase table (erase.hip): erase_count records (one per non-empty box)
   // from block erase_at, behind every stage's entries and the blur table, for
   // erase_units workgroups writing erase_elem (mxd_erase_elem) elements, CHW or
@@ -516,6 +520,19 @@ int gaussian_weights(float sigma, int32_t k, float* out);
 // rows per step, chosen by measurement; mxd_blur_shape overrides them.
 constexpr int32_t kBlurSegRows = 112, kBlurStep = 8;
 extern std::atomic<int32_t> g_blur_seg_rows, g_blur_step;
+// What MXD_ENHANCE_PIL_GAUSSIAN_BLUR / PIL_BOX_BLUR make of a radius
+// (mxd_pil_blur_params): the box radius, the two weights of a pass and the
+// passes per axis.  fr is NaN or out of range for a radius the calls refuse.
+struct PilBlurParams {
+  float fr;
+  uint32_t ww, fw;
+  int32_t passes;
+};
+PilBlurParams pil_blur_params(int32_t op, float radius);
+inline bool pil_blur_op(int32_t op) { return op == MXD_ENHANCE_PIL_GAUSSIAN_BLUR || op == MXD_ENHANCE_PIL_BOX_BLUR; }
+// pilblur_rows' output rows per segment: chosen by
+// reading the code, not measured.
+constexpr int32_t kPilBlurSegRows = 112;
 
 // ---------------------------------------------------------------------------
 // MixUp / CutMix (mix.cpp).

@@ -3,11 +3,13 @@
 // in plain C++, and the validation of the _enhance calls.  The arithmetic is
 // Pillow's ImageEnhance.Sharpness / Color / Brightness, bit for bit, and for
 // GAUSSIAN_BLUR a separable Gaussian with torchvision's kernel and reflect
-// padding.  The device side is enhance.hip and blur.hip;
-// the two sides share no code.
+// padding, and for PIL_GAUSSIAN_BLUR / PIL_BOX_BLUR Pillow's fixed-point box
+// passes.  The device side is enhance.hip, blur.hip and
+// pilblur.hip; the two sides share no code.
 // Host only.
 #include "capi_internal.h"
 
+#include <algorithm>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -29,6 +31,13 @@ int enhance_check(const mxd_enhance& e, int32_t i) {
       return at("reserved[0] (the kernel size) must be odd and in 3..33");
     if (!(std::isfinite(e.factor) && e.factor > 0.0f && e.factor <= 1e6f))
       return at("factor (sigma) must be finite, > 0 and at most 1e6");
+    return MXD_OK;
+  }
+  if (e.op == MXD_ENHANCE_PIL_GAUSSIAN_BLUR || e.op == MXD_ENHANCE_PIL_BOX_BLUR) {
+    if (e.reserved[0] != 0 || e.reserved[1] != 0) return at("reserved must be 0");
+    if (!(std::isfinite(e.factor) && e.factor >= 0.0f)) return at("factor (the radius) must be finite and not negative");
+    if (!(pil_blur_params(e.op, e.factor).fr < (float)mxd::kBlurMaxR))
+      return at("factor (the radius) is too large: its box radius must stay below " + std::to_string(mxd::kBlurMaxR));
     return MXD_OK;
   }
   if (e.op < MXD_ENHANCE_NONE || e.op > MXD_ENHANCE_BRIGHTNESS) return at("unknown op " + std::to_string(e.op));
@@ -94,7 +103,67 @@ void gaussian_blur(const uint8_t* rgb, int w, int h, int64_t stride, const float
     }
 }
 
+// One pass of Pillow's extended box blur over n bytes `step` apart.
+void box_pass(const uint8_t* in, uint8_t* out, int n, int64_t step, int R, uint32_t ww, uint32_t fw) {
+  auto at = [&](int i) { return (uint32_t)in[(int64_t)std::min(std::max(i, 0), n - 1) * step]; };
+  for (int x = 0; x < n; x++) {
+    uint32_t sum = 0;
+    for (int d = -R; d <= R; d++) sum += at(x + d);
+    out[(int64_t)x * step] = (uint8_t)((ww * sum + fw * (at(x - R - 1) + at(x + R + 1)) + (1u << 23)) >> 24);
+  }
+}
+
+// PIL_GAUSSIAN_BLUR / PIL_BOX_BLUR (mxd_amd.h): the passes over every row,
+// then over every column of the result, each on the bytes of the one before.
+void pil_blur(const uint8_t* rgb, int w, int h, int64_t stride, const PilBlurParams& p, uint8_t* out, int64_t out_stride) {
+  const int n = w * 3, R = (int)p.fr;
+  std::vector<uint8_t> a((size_t)h * n), b((size_t)h * n);
+  for (int y = 0; y < h; y++) std::memcpy(&a[(size_t)y * n], rgb + (int64_t)y * stride, n);
+  for (int pass = 0; pass < 2 * p.passes && p.fr != 0.0f; pass++) {
+    if (pass < p.passes) {
+      for (int y = 0; y < h; y++)
+        for (int c = 0; c < 3; c++) box_pass(&a[(size_t)y * n + c], &b[(size_t)y * n + c], w, 3, R, p.ww, p.fw);
+    } else {
+      for (int i = 0; i < n; i++) box_pass(&a[i], &b[i], h, n, R, p.ww, p.fw);
+    }
+    a.swap(b);
+  }
+  for (int y = 0; y < h; y++) std::memcpy(out + (int64_t)y * out_stride, &a[(size_t)y * n], n);
+}
+
 }  // namespace
+
+// Pillow's _gaussian_blur_radius and the weights of ImagingLineBoxBlur8: all
+// float32 (volatile: no operation is contracted or carried wider) but the
+// square root.
+PilBlurParams pil_blur_params(int32_t op, float radius) {
+  PilBlurParams p{};
+  p.passes = op == MXD_ENHANCE_PIL_GAUSSIAN_BLUR ? 3 : 1;
+  volatile float fr = radius;
+  if (op == MXD_ENHANCE_PIL_GAUSSIAN_BLUR) {
+    volatile float s2 = radius * radius;
+    s2 = s2 / 3.0f;
+    volatile float L = (float)std::sqrt(12.0 * (double)s2 + 1.0);
+    volatile float l = std::floor((L - 1.0f) / 2.0f);
+    volatile float t = l * (l + 1.0f);
+    volatile float u = 3.0f * s2;
+    t = t - u;
+    volatile float a = (2.0f * l + 1.0f) * t;
+    volatile float l1 = (l + 1.0f) * (l + 1.0f);
+    volatile float den = s2 - l1;
+    den = 6.0f * den;
+    a = a / den;
+    fr = l + a;
+  }
+  p.fr = fr;
+  if (!(p.fr >= 0.0f && p.fr < 1e6f)) return p;  // (not valid: the caller refuses it)
+  volatile float span = p.fr * 2.0f;
+  span = span + 1.0f;
+  volatile float q = (float)(1 << 24) / span;
+  p.ww = (uint32_t)q;
+  p.fw = ((1u << 24) - (2u * (uint32_t)(int)p.fr + 1u) * p.ww) / 2u;
+  return p;
+}
 
 int gaussian_weights(float sigma, int32_t k, float* out) {
   const int R = (k - 1) / 2;
@@ -135,6 +204,19 @@ extern "C" int mxd_blur_shape(int32_t seg_rows, int32_t step) {
   return MXD_OK;
 }
 
+extern "C" int mxd_pil_blur_params(int32_t op, float radius, float* fr, uint32_t* ww, uint32_t* fw, int32_t* passes) {
+  if (op != MXD_ENHANCE_PIL_GAUSSIAN_BLUR && op != MXD_ENHANCE_PIL_BOX_BLUR)
+    return fail(MXD_ERR_INVALID, "mxd_pil_blur_params: op must be MXD_ENHANCE_PIL_GAUSSIAN_BLUR or MXD_ENHANCE_PIL_BOX_BLUR");
+  const mxd_enhance e{op, radius, {0, 0}};
+  if (int rc = mxd_enhance_validate(&e)) return rc;
+  const PilBlurParams p = pil_blur_params(op, radius);
+  if (fr) *fr = p.fr;
+  if (ww) *ww = p.ww;
+  if (fw) *fw = p.fw;
+  if (passes) *passes = p.passes;
+  return MXD_OK;
+}
+
 extern "C" int mxd_gaussian_weights(float sigma, int32_t k, float* out) {
   const mxd_enhance e{MXD_ENHANCE_GAUSSIAN_BLUR, sigma, {k, 0}};
   if (int rc = mxd_enhance_validate(&e)) return rc;
@@ -160,6 +242,10 @@ extern "C" int mxd_enhance_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, in
     float wt[33];
     gaussian_weights(f, enh->reserved[0], wt);
     gaussian_blur(rgb, w, h, stride, wt, (enh->reserved[0] - 1) / 2, out, out_stride);
+    return MXD_OK;
+  }
+  if (op == MXD_ENHANCE_PIL_GAUSSIAN_BLUR || op == MXD_ENHANCE_PIL_BOX_BLUR) {
+    pil_blur(rgb, w, h, stride, pil_blur_params(op, f), out, out_stride);
     return MXD_OK;
   }
   for (int y = 0; y < h; y++)

@@ -830,8 +830,8 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
     return out;
   }
   ImagePlan p = geometry_view(img);
-  if ((p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) || (p.enhanced && (p.enhance_op == MXD_ENHANCE_SHARPNESS || p.enhance_op == MXD_ENHANCE_GAUSSIAN_BLUR))) {
-    // the op's statistics (SHARPNESS: copied ring; GAUSSIAN_BLUR: reflected edges) are those of the window it saw: run it, crop its bytes
+  if ((p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) || (p.enhanced && (p.enhance_op == MXD_ENHANCE_SHARPNESS || p.enhance_op >= MXD_ENHANCE_GAUSSIAN_BLUR))) {
+    // the op's statistics (SHARPNESS: copied ring; GAUSSIAN_BLUR: reflected edges; the PIL blurs: clamped edges) are those of the window it saw: run it, crop its bytes
     img->data();
     p = view(img);
   }
@@ -1366,6 +1366,8 @@ std::shared_ptr<Array> ImageRandomErasing::apply_video(const std::shared_ptr<Arr
 const char* enhance_name(int32_t op) {
   static const char* const names[] = {"none", "sharpness", "color", "brightness"};
   if (op == MXD_ENHANCE_GAUSSIAN_BLUR) return "gaussian_blur";
+  if (op == MXD_ENHANCE_PIL_GAUSSIAN_BLUR) return "pil_gaussian_blur";
+  if (op == MXD_ENHANCE_PIL_BOX_BLUR) return "pil_box_blur";
   return op >= 0 && op <= MXD_ENHANCE_BRIGHTNESS ? names[op] : "none";
 }
 
@@ -1375,8 +1377,16 @@ namespace {
 bool enhance_factor_ok(double f) { return std::isfinite(f) && f >= 0.0 && f <= 1e6; }
 }  // namespace
 
-// A blur's sigma is checked as the float32 the launch takes.
+// A blur's sigma or radius is checked as the float32 the launch takes.
 void ImageEnhance::check_args(const char* what) const {
+  if (op_ == MXD_ENHANCE_PIL_GAUSSIAN_BLUR || op_ == MXD_ENHANCE_PIL_BOX_BLUR) {
+    // (the box radius grows with the radius: the two ends of a range speak for what lies between)
+    for (double r : {lo_, hi_})
+      if (!std::isfinite(r) || mxd_pil_blur_params(op_, (float)r, nullptr, nullptr, nullptr, nullptr) != MXD_OK)
+        throw std::invalid_argument(name() + ": radius" + what +
+                                    " must be finite, not negative and small enough that its box radius stays below 16");
+    return;
+  }
   if (op_ != MXD_ENHANCE_GAUSSIAN_BLUR) {
     if (!enhance_factor_ok(lo_) || !enhance_factor_ok(hi_))
       throw std::invalid_argument(name() + ": factor" + what + " must be finite and in 0..1e6");
@@ -1399,7 +1409,8 @@ ImageEnhance::ImageEnhance(std::string ikey, int32_t op, std::pair<double, doubl
       ksize_(ksize) {
   check_args(" range");
   if (lo_ > hi_)
-    throw std::invalid_argument(name() + (op_ == MXD_ENHANCE_GAUSSIAN_BLUR ? ": sigma" : ": factor") + " range has lo > hi");
+    throw std::invalid_argument(name() + (op_ == MXD_ENHANCE_GAUSSIAN_BLUR ? ": sigma" : op_ >= MXD_ENHANCE_PIL_GAUSSIAN_BLUR ? ": radius" : ": factor") +
+                                " range has lo > hi");
 }
 
 double ImageEnhance::factor() const {

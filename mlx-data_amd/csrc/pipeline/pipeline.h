@@ -133,6 +133,9 @@ struct ImagePlan {
   // form are MXD_ENHANCE_GAUSSIAN_BLUR (enhance_factor: sigma; enhance_ksize:
   // the kernel size) with SHARPNESS's rules: the symmetric form of the blur
   // makes the flip compose, and its reflected edges are the uncropped window's.
+  // image_pil_gaussian_blur, its random form and image_pil_box_blur are
+  // MXD_ENHANCE_PIL_GAUSSIAN_BLUR / PIL_BOX_BLUR (enhance_factor: Pillow's
+  // radius) with the same rules: a box pass is symmetric, its edges clamp.
   bool enhanced = false;
   int32_t enhance_op = 0;
   float enhance_factor = 1.0f;
@@ -475,6 +478,10 @@ std::array<double, 6> affine_rotate_matrix(int64_t w, int64_t h, double angle);
 // MXD_ENHANCE_GAUSSIAN_BLUR (image_gaussian_blur) is torchvision's
 // GaussianBlur: factor is sigma (finite, > 0 as a float32, <= 1e6) and ksize
 // the kernel size (odd, 3..33); every other op takes ksize 0.
+// MXD_ENHANCE_PIL_GAUSSIAN_BLUR (image_pil_gaussian_blur) and
+// MXD_ENHANCE_PIL_BOX_BLUR (image_pil_box_blur) are Pillow's
+// ImageFilter.GaussianBlur / BoxBlur: factor is the radius, as
+// mxd_pil_blur_params accepts it.
 class ImageEnhance : public ImageOp {
  public:
   // op: mxd_enhance_op (not NONE); factor: finite, 0 <= factor <= 1e6.
@@ -495,7 +502,7 @@ class ImageEnhance : public ImageOp {
   double lo_, hi_;
   int32_t ksize_;
 };
-// "sharpness", "color", "brightness", "gaussian_blur" of an mxd_enhance_op (the op is image_<name>).
+// "sharpness", "color", "brightness", "gaussian_blur", "pil_gaussian_blur", "pil_box_blur" of an mxd_enhance_op (the op is image_<name>).
 const char* enhance_name(int32_t op);
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the

@@ -678,6 +678,30 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
           },
           py::arg("key"), py::arg("kernel_size"), py::arg("sigma") = py::make_tuple(0.1, 2.0), py::arg("output_key") = "")
       .def(
+          "image_pil_gaussian_blur",
+          [wrap](const Self& self, const std::string& key, double radius, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_PIL_GAUSSIAN_BLUR, radius, output_key));
+          },
+          py::arg("key"), py::arg("radius"), py::arg("output_key") = "")
+      .def(
+          "image_random_pil_gaussian_blur",
+          [wrap](const Self& self, const std::string& key, const py::object& radius, const std::string& output_key) {
+            std::pair<double, double> range;
+            try {
+              range = radius.cast<std::pair<double, double>>();
+            } catch (const py::cast_error&) {
+              throw std::invalid_argument("image_random_pil_gaussian_blur: radius must be a (lo, hi) pair");
+            }
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_PIL_GAUSSIAN_BLUR, range, output_key));
+          },
+          py::arg("key"), py::arg("radius") = py::make_tuple(0.1, 2.0), py::arg("output_key") = "")
+      .def(
+          "image_pil_box_blur",
+          [wrap](const Self& self, const std::string& key, double radius, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_PIL_BOX_BLUR, radius, output_key));
+          },
+          py::arg("key"), py::arg("radius"), py::arg("output_key") = "")
+      .def(
           "image_color",
           [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
             return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_COLOR, factor, output_key));

@@ -272,7 +272,8 @@ int launch_warp_cubic(const WarpRowDev* rows, int nimgs, int tile_first, int til
 // stage cannot run in place: src and dst are different rows.
 constexpr int kEnhTileW = 64, kEnhTileH = 16;
 // mxd_enhance_op's values.
-enum EnhanceOp : int32_t { kEnhNone = 0, kEnhSharpness = 1, kEnhColor = 2, kEnhBrightness = 3, kEnhGaussianBlur = 8 };
+enum EnhanceOp : int32_t { kEnhNone = 0, kEnhSharpness = 1, kEnhColor = 2, kEnhBrightness = 3, kEnhGaussianBlur = 8,
+                           kEnhPilGaussianBlur = 9, kEnhPilBoxBlur = 10 };
 struct EnhanceRowDev {
   const uint8_t* src;  // u8 rows (16-byte aligned base, stride a multiple of 16)
   uint8_t* dst;        // scratch rows like src, or the caller's u8 destination (any alignment)
@@ -306,6 +307,23 @@ struct BlurRecDev {
 static_assert(sizeof(BlurRecDev) == 96, "BlurRecDev layout");
 // step: source rows per step of the walk, 4 or 8.
 int launch_blur(const EnhanceRowDev* rows, const BlurRecDev* recs, int nrecs, int nunits, int step, void* stream);
+// Pillow's GaussianBlur / BoxBlur of the enhance stage (pilblur.hip): the
+// images whose op is kEnhPilGaussianBlur or kEnhPilBoxBlur (box radius above 0)
+// have no tile in enhance_rows either and one record in a table behind the blur
+// table.  pilblur_rows takes the same strip x segment units as blur_rows and
+// reads the image's rows from its enhance entry.  A pass reaches R + 1 <=
+// kBlurMaxR pixels; R, ww, fw and the pass count are part of the uploaded bytes.
+struct PilBlurRecDev {
+  int32_t entry;       // the image's entry among the enhance stage's
+  int32_t unit_begin;  // first of the image's workgroups among the launch's
+  int32_t strips;      // strips per row of segments
+  int32_t seg_rows;    // output rows per segment
+  int32_t R;           // (int)fr: the whole pixels of the box radius, 0..kBlurMaxR - 1
+  uint32_t ww, fw;     // the 8.24 weights of a box pixel and of the two pixels beyond it
+  int32_t passes;      // passes per axis: 3 (Gaussian) or 1 (box)
+};
+static_assert(sizeof(PilBlurRecDev) == 32, "PilBlurRecDev layout");
+int launch_pilblur(const EnhanceRowDev* rows, const PilBlurRecDev* recs, int nrecs, int nunits, void* stream);
 // The mix stage (mix.hip): the last stage of a mix call (mxd_mix), over u8 RGB
 // scratch rows.  One entry per image; a workgroup takes kMixRows rows of one
 // image, workgroups numbered through blk_begin.  It reads the image's rows

@@ -49,6 +49,7 @@ EXPORTS = (
     "mxd_warp_validate", "mxd_warp_apply_u8", "mxd_resize_crop_batch_warp", "mxd_resize_crop_to_device_warp",
     "mxd_jpeg_resize_crop_to_device_warp",
     "mxd_enhance_validate", "mxd_enhance_apply_u8", "mxd_gaussian_weights", "mxd_blur_shape",
+    "mxd_pil_blur_params",
     "mxd_resize_crop_batch_enhance",
     "mxd_resize_crop_to_device_enhance", "mxd_jpeg_resize_crop_to_device_enhance",
     "mxd_mix_validate", "mxd_mix_apply_u8", "mxd_resize_crop_batch_mix", "mxd_resize_crop_to_device_mix",
@@ -476,6 +477,8 @@ MXD_ENHANCE_SHARPNESS = 1
 MXD_ENHANCE_COLOR = 2
 MXD_ENHANCE_BRIGHTNESS = 3
 MXD_ENHANCE_GAUSSIAN_BLUR = 8  # factor: sigma; a third tuple member: the kernel size
+MXD_ENHANCE_PIL_GAUSSIAN_BLUR = 9  # factor: the radius of Pillow's ImageFilter.GaussianBlur
+MXD_ENHANCE_PIL_BOX_BLUR = 10  # factor: the radius of Pillow's ImageFilter.BoxBlur
 
 
 class MxdEnhance(ctypes.Structure):
@@ -485,7 +488,8 @@ class MxdEnhance(ctypes.Structure):
 
 
 def make_enhances(enhances):
-    """(op, factor) tuples -- (MXD_ENHANCE_GAUSSIAN_BLUR, sigma, kernel_size) for a blur --
+    """(op, factor) tuples -- (MXD_ENHANCE_GAUSSIAN_BLUR, sigma, kernel_size) for a blur,
+    (MXD_ENHANCE_PIL_GAUSSIAN_BLUR, radius) or (MXD_ENHANCE_PIL_BOX_BLUR, radius) for Pillow's --
     (or MxdEnhance values) -> ctypes array of mxd_enhance."""
     arr = (MxdEnhance * max(1, len(enhances)))()
     for i, e in enumerate(enhances):
@@ -504,6 +508,14 @@ def gaussian_weights(sigma, kernel_size):
     out = np.zeros(max(1, int(kernel_size)), np.float32)
     check(lib().mxd_gaussian_weights(ctypes.c_float(sigma), int(kernel_size), ctypes.c_void_p(out.ctypes.data)))
     return out[:int(kernel_size)]
+
+
+def pil_blur_params(op, radius):
+    """mxd_pil_blur_params: (fr, ww, fw, passes) of a Pillow blur op and its radius."""
+    fr, ww, fw, passes = ctypes.c_float(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int32()
+    check(lib().mxd_pil_blur_params(int(op), ctypes.c_float(radius), ctypes.byref(fr), ctypes.byref(ww),
+                                    ctypes.byref(fw), ctypes.byref(passes)))
+    return fr.value, ww.value, fw.value, passes.value
 
 
 def blur_shape(seg_rows=0, step=0):

@@ -152,6 +152,17 @@ for bit (``include/mxd_amd.h``).  It composes as ``image_sharpness`` does: a
 flip, tone and colour ops and the output forms after it; a crop, resize,
 ``image_rotate``, warp or second enhance op materialises what is pending.
 
+``image_pil_gaussian_blur(key, radius)``,
+``image_random_pil_gaussian_blur(key, radius=(lo, hi))`` and
+``image_pil_box_blur(key, radius)`` are Pillow's ``ImageFilter.GaussianBlur``
+and ``ImageFilter.BoxBlur``, byte for byte: the blur of the loaders that call
+``ImageFilter.GaussianBlur(radius=random.uniform(0.1, 2.0))`` on a PIL image
+(MoCo v2 / v3, DINO, Barlow Twins, VICReg, DeiT III's 3-Augment), which
+``image_gaussian_blur`` does not reproduce.  The radius is finite, not negative
+and at most about 16.4 (Gaussian) or below 16 (box); radius 0 leaves the image
+as it is; the random form draws one uniform radius per image (a video draws
+once).  They compose exactly as ``image_gaussian_blur`` does.
+
 ``image_random_erasing(key, prob=0.5, area=(0.02, 1/3), aspect=(0.3, 1/0.3),
 mode="const" | "rand" | "pixel", count=1 | (lo, hi), value=0.0,
 output_key="")`` (with ``image_random_erasing_if``) is timm's ``RandomErasing``
@@ -239,7 +250,8 @@ def _add_if_variants(cls):
                  "image_random_translate", "image_random_affine_rotate",
                  "image_sharpness", "image_color", "image_brightness", "image_random_sharpness",
                  "image_random_color", "image_random_brightness", "image_gaussian_blur",
-                 "image_random_gaussian_blur", "image_random_erasing"):
+                 "image_random_gaussian_blur", "image_pil_gaussian_blur", "image_random_pil_gaussian_blur",
+                 "image_pil_box_blur", "image_random_erasing"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 

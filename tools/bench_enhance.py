@@ -31,6 +31,20 @@ process for --rounds rounds (3 rounds: 9 windows each):
           round, clamp, / 255, normalise, permute and cast to bfloat16
   a, a2, n as above; c is not run
 
+--op pilblur times Pillow's GaussianBlur:
+
+  p       mxd_resize_crop_batch_enhance, MXD_ENHANCE_PIL_GAUSSIAN_BLUR with
+          radius 2 for every image (pilblur_rows), the same format
+  p16     as p with radius 16: the design claims a cost that does not grow
+          with the radius beyond the wider halo
+  g       MXD_ENHANCE_GAUSSIAN_BLUR with k = 23 and sigma 2.0 (blur_rows) on
+          the same images
+  d       the u8 mxd_resize_crop_batch, then torch on the same stream: the six
+          box passes (torch_pil_blur: replicate pad, a ones convolution, the
+          8.24 weights in int64, the byte rounding after every pass), / 255,
+          normalise, permute and cast to bfloat16
+  a, a2, n as above
+
 --variants picks a subset (a profiler run of the enhance call alone: --variants b).
 --lib times another build of the library: enhance.hip compiled with
 -DMXD_ENH_LDS stages the tile and its halo in LDS instead of reading the
@@ -57,6 +71,25 @@ FACTOR = 1.5
 
 
 BLUR_K, BLUR_SIGMA = 23, 2.0
+PIL_RADIUS, PIL_RADIUS_WIDE = 2.0, 16.0
+
+
+def torch_pil_blur(torch, x, R, ww, fw, passes):
+    """Pillow's box passes on a float32 (B, C, H, W) tensor of byte values: the sums
+    stay below 2^24, so float32 holds them exactly; the weights apply in int64."""
+    import torch.nn.functional as F
+
+    C = x.shape[1]
+    ones = torch.ones((C, 1, 1, 2 * R + 1), dtype=torch.float32, device=x.device)
+    for axis in (3, 2):
+        for _ in range(passes):
+            t = x if axis == 3 else x.transpose(2, 3)
+            tp = F.pad(t, (R + 1, R + 1, 0, 0), mode="replicate")
+            box = F.conv2d(tp[..., 1:-1], ones, groups=C)
+            far = tp[..., :-2 * (R + 1)] + tp[..., 2 * (R + 1):]
+            t = ((box.long() * ww + far.long() * fw + (1 << 23)) >> 24).float()
+            x = t if axis == 3 else t.transpose(2, 3)
+    return x
 
 
 def run_workload(name, capi, torch, rounds, emit, only, op="sharpness", blur_shapes=()):
@@ -138,6 +171,20 @@ def run_workload(name, capi, torch, rounds, emit, only, op="sharpness", blur_sha
 
         every = {"a": a, "b": enhance_call(blur), "n": enhance_call(none), "d": d_blur, "a2": a}
         every.update({f"b{seg}_{step}": shaped(seg, step) for seg, step in blur_shapes})
+    if op == "pilblur":
+        gauss = capi.MXD_ENHANCE_PIL_GAUSSIAN_BLUR
+        fr, ww, fw, passes = capi.pil_blur_params(gauss, PIL_RADIUS)
+
+        def d_pil(i):
+            call(L.mxd_resize_crop_batch(arrays["u8"][i % 2], B, capi.MXD_U8, dev, hs))
+            with torch.cuda.stream(ext):
+                y = torch_pil_blur(torch, u8s[i % 2].permute(0, 3, 1, 2).float(), int(fr), ww, fw, passes)
+                ((y / 255 - mean_t) / std_t).to(torch.bfloat16)
+
+        every = {"a": a, "p": enhance_call(capi.make_enhances([(gauss, PIL_RADIUS)] * B)),
+                 "p16": enhance_call(capi.make_enhances([(gauss, PIL_RADIUS_WIDE)] * B)),
+                 "g": enhance_call(capi.make_enhances([(capi.MXD_ENHANCE_GAUSSIAN_BLUR, BLUR_SIGMA, BLUR_K)] * B)),
+                 "n": enhance_call(none), "d": d_pil, "a2": a}
     variants = {k: f for k, f in every.items() if not only or k in only}
     try:
         for f in variants.values():  # every shape and variant warmed first
@@ -153,7 +200,13 @@ def run_workload(name, capi, torch, rounds, emit, only, op="sharpness", blur_sha
             med[k] = statistics.median(w)
             emit({"workload": name, "variant": k, "images": B, "ms_per_launch": round(med[k], 5), "min": min(w),
                   "max": max(w), "windows": w})
-        if not only and op == "blur":
+        if not only and op == "pilblur":
+            lo = min(med["a"], med["a2"])
+            emit({"workload": name, "summary": True, "op": "pil_gaussian_blur", "radius": PIL_RADIUS,
+                  "p_over_a": round(med["p"] / lo, 4), "n_over_a": round(med["n"] / lo, 4),
+                  "p_over_g": round(med["p"] / med["g"], 4), "d_over_p": round(med["d"] / med["p"], 2),
+                  "p16_over_p": round(med["p16"] / med["p"], 4), "a_spread": round(abs(med["a"] - med["a2"]) / lo, 4)})
+        elif not only and op == "blur":
             lo = min(med["a"], med["a2"])
             emit({"workload": name, "summary": True, "op": "gaussian_blur", "k": BLUR_K, "sigma": BLUR_SIGMA,
                   "b_over_a": round(med["b"] / lo, 4), "n_over_a": round(med["n"] / lo, 4),
@@ -178,7 +231,7 @@ def main():
     ap.add_argument("--workloads", default="c2,c4")
     ap.add_argument("--variants", default="")
     ap.add_argument("--out", default="")
-    ap.add_argument("--op", default="sharpness", choices=("sharpness", "blur"))
+    ap.add_argument("--op", default="sharpness", choices=("sharpness", "blur", "pilblur"))
     ap.add_argument("--blur-shapes", default="", help="--op blur: segment rows : rows per step, e.g. 32:8,112:8,56:4")
     ap.add_argument("--lib", default="", help="another build of libmxd_amd.so to time (a compile-time variant)")
     args = ap.parse_args()
