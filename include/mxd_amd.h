@@ -87,7 +87,10 @@ extern "C" {
  * mxd_resize_crop_batch_erase, mxd_resize_crop_to_device_erase,
  * mxd_jpeg_resize_crop_to_device_erase.
  * 7, added without a new number (test for MXD_HAS_WARP_CUBIC): the warp mode
- * MXD_WARP_BICUBIC. */
+ * MXD_WARP_BICUBIC.
+ * 7, added without a new number (test for MXD_HAS_PIL_RESIZE / the symbol):
+ * Pillow's 8-bit resize -- the mxd_filter values MXD_FILTER_PIL_BILINEAR,
+ * MXD_FILTER_PIL_BICUBIC, MXD_FILTER_PIL_LANCZOS and mxd_pil_resize_u8. */
 #define MXD_ABI_VERSION 7
 #define MXD_HAS_FILTERS 1
 #define MXD_HAS_COLOR 1
@@ -99,6 +102,7 @@ extern "C" {
 #define MXD_HAS_GAUSSIAN_BLUR 1
 #define MXD_HAS_PIL_BLUR 1
 #define MXD_HAS_ERASE 1
+#define MXD_HAS_PIL_RESIZE 1
 
 enum mxd_status {
   MXD_OK = 0,
@@ -127,12 +131,40 @@ enum mxd_dtype {
  * Downsampling widens the kernel by 1/scale (antialiasing); edges clamp; each
  * output's weights are renormalised to sum 1; negative lobes may overshoot and
  * the u8 encode clamps them.  An axis with out == in is the identity for every
- * filter.  Any other value: MXD_ERR_INVALID. */
+ * filter.
+ *
+ * The MXD_FILTER_PIL_* values (feature test: MXD_HAS_PIL_RESIZE) are Pillow's
+ * 8-bit resize, byte for byte: Image.resize(size, BILINEAR / BICUBIC / LANCZOS)
+ * of an L or RGB image, hence torchvision's Resize / RandomResizedCrop on PIL
+ * images and timm's loaders.  (MXD_FILTER_CATMULLROM is the same kernel in
+ * float32 arithmetic: within +-1 of Pillow, not equal.)  Pillow's arithmetic
+ * (Resample.c), per axis in -> out with support s = 1 / 2 / 3, all in double:
+ *   scale = in / out, fs = max(scale, 1), support = s fs; for output xx:
+ *   center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0),
+ *   xmax = min((int)(center + support + 0.5), in),
+ *   w[x] = f((x + xmin - center + 0.5) (1 / fs)) for x < xmax - xmin, divided by
+ *   their sequential sum, k[x] = (int)(w < 0 ? -0.5 + w 2^22 : 0.5 + w 2^22);
+ *   f: bilinear 1 - |x| on |x| < 1; bicubic, a = -0.5: ((a+2)x - (a+3))x^2 + 1
+ *   on x < 1, (((x-5)x + 8)x - 4)a on x < 2; Lanczos sinc(x) sinc(x/3) on
+ *   -3 <= x < 3.
+ * One pass is out = clamp((2^21 + sum pixel k) >> 22, 0, 255) in int32.  The
+ * horizontal pass runs first, into bytes; the vertical pass runs on those
+ * bytes.  An axis with out == in has k = 2^22 at the centre and 0 elsewhere
+ * (Pillow skips the pass).  1 and 3 channels only (Pillow premultiplies the
+ * alpha of LA / RGBA): 2 and 4 are MXD_ERR_UNSUPPORTED, as is an axis with more
+ * than 128 taps (a 16 : 1 Lanczos downscale has 97).  Every kernel policy runs
+ * these images on one kernel (pil_resize_rows); a call may mix them with
+ * images of the float filters.  The crop window and the flip mean what they
+ * mean for the other filters.
+ * Any other value: MXD_ERR_INVALID. */
 enum mxd_filter {
   MXD_FILTER_TRIANGLE = 0,
   MXD_FILTER_CATMULLROM = 1,
   MXD_FILTER_MITCHELL = 2,
-  MXD_FILTER_CUBICBSPLINE = 3
+  MXD_FILTER_CUBICBSPLINE = 3,
+  MXD_FILTER_PIL_BILINEAR = 16,
+  MXD_FILTER_PIL_BICUBIC = 17,
+  MXD_FILTER_PIL_LANCZOS = 18
 };
 
 /*
@@ -196,9 +228,19 @@ int mxd_center_crop_origin(int64_t w, int64_t h, int64_t cw, int64_t ch, int64_t
  * MXD_ERR_INVALID is returned. */
 int mxd_axis_taps(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t crop_len, int32_t max_taps,
                   int32_t* first, int32_t* ntaps, float* weights, int32_t* taps_needed);
-/* The same for any mxd_filter (mxd_axis_taps is its filter-0 form). */
+/* The same for any mxd_filter (mxd_axis_taps is its filter-0 form).  For a
+ * MXD_FILTER_PIL_* filter the weights are the 8.22 coefficients as k / 2^22,
+ * exact in float32 (|k| < 2^24): k = (int32_t)(weight * 4194304.0f). */
 int mxd_axis_taps_filter(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t crop_len, int32_t filter,
                          int32_t max_taps, int32_t* first, int32_t* ntaps, float* weights, int32_t* taps_needed);
+/* The CPU statement of the MXD_FILTER_PIL_* filters (host only, plain loops
+ * over the tables above): resizes the src_w x src_h image at src (1 or 3
+ * channels, rows src_stride bytes apart) to resize_w x resize_h and writes the
+ * crop window, mirrored when flip is nonzero, to dst.  What the kernel
+ * computes, and what Pillow's Image.resize does. */
+int mxd_pil_resize_u8(const uint8_t* src, int64_t src_stride, int32_t src_w, int32_t src_h, int32_t channels,
+                      int32_t filter, int32_t resize_w, int32_t resize_h, int32_t crop_x, int32_t crop_y,
+                      int32_t crop_w, int32_t crop_h, int32_t flip, uint8_t* dst, int64_t dst_stride);
 
 /* ---- the hot path -------------------------------------------------------- */
 
@@ -309,14 +351,15 @@ int mxd_set_tuning(int32_t knob, int32_t value);
 
 /* The wave-kernel plan of one image on `device`, i.e. what runs when the
  * band kernel declines it or is off (diagnostics, tests): info[0] = 1 wave
- * kernel / 0 general kernel, then kind
+ * kernel / 0 general kernel / 2 pil_resize_rows (a MXD_FILTER_PIL_* image,
+ * under every policy; the rest is then unset), then kind
  * (0 gather, 2 scatter), tap bucket, scatter S, scatter DMAX, output pixels
  * per lane, strips, source pixels per lane (RGB 16: byte lanes, 16 bytes per
  * lane).  Host only: needs no device. */
 int mxd_describe_plan(const mxd_image* image, int32_t out_dtype, int32_t device, int32_t* info8);
 
 /* The band-kernel plan of one image (host only): info[0] = 1 when the band
- * kernel takes it (under the current policy), then horizontal tap class, row
+ * kernel takes it (under the current policy; never a MXD_FILTER_PIL_* image), then horizontal tap class, row
  * slots per group (DB), accumulator slots, source window KiB per strip row,
  * strips, strip columns, prologue groups, most new source rows per output
  * row, groups in flight, LDS bytes per workgroup, 0. */

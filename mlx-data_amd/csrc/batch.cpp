@@ -167,7 +167,10 @@ int validate(const mxd_image& im, int32_t i) {
   if (im.crop_x + im.crop_w > im.resize_w || im.crop_y + im.crop_h > im.resize_h)
     return at("Array: sub: shape out of bound");
   if (im.src_stride < (int64_t)im.src_w * im.channels) return at("mxd: src_stride smaller than a row");
-  if (im.filter < 0 || im.filter >= mxd::kFilterCount) return at("mxd: unknown filter");
+  if (!mxd::filter_is_valid(im.filter)) return at("mxd: unknown filter");
+  if (mxd::filter_is_pil(im.filter) && im.channels != 1 && im.channels != 3)
+    return fail(MXD_ERR_UNSUPPORTED, "mxd: the Pillow filters take 1 or 3 channels: Pillow premultiplies the alpha of "
+                                     "LA / RGBA (image " + std::to_string(i) + ")");
   return MXD_OK;
 }
 
@@ -384,8 +387,10 @@ int launch_all(const BatchLayout& L, const ImgDev* dev, Workspace* ws, const mxd
       mxd::WaveCfg cfg = g.cfg;
       cfg.prio = nfork == 0 ? 1 : 0;  // priorities only where launches never overlap
       rc = ofd ? mxd::launch_wave_fmt(cfg, dev + g.first, *ofd, s) : mxd::launch_wave(cfg, dev + g.first, s);
-    } else {
+    } else if (L.launches[k].kind == 2) {
       rc = mxd::launch_resample(L.general, dev + L.general_at, s);
+    } else {
+      rc = mxd::launch_pil_resize(L.pil, dev + L.pil_at, s);
     }
     if (rc) {
       launch_rc = fail(MXD_ERR_DEVICE, std::string("resample launch failed: ") + hipGetErrorString(hipGetLastError()) +

@@ -51,7 +51,16 @@ int plan_images(Batch& b) {
     }
     if (int rc = b.env.tables->get(b.device, im.src_w, im.resize_w, &p.xt, im.filter)) return rc;
     if (int rc = b.env.tables->get(b.device, im.src_h, im.resize_h, &p.yt, im.filter)) return rc;
-    if (st.ycc) {
+    if (mxd::filter_is_pil(im.filter)) {
+      // Pillow's integer arithmetic is pil_resize_rows' alone, under every policy.
+      // (validate() refused 2 and 4 channels)
+      if (std::max(p.xt->width, p.yt->width) > mxd::kPilMaxTaps)
+        return fail(MXD_ERR_UNSUPPORTED, "mxd: the Pillow filters take at most " + std::to_string(mxd::kPilMaxTaps) +
+                                             " taps per axis (image " + std::to_string(i) + ": " +
+                                             std::to_string(std::max(p.xt->width, p.yt->width)) + ")");
+      if (st.ycc) return fail(MXD_ERR_UNSUPPORTED, "mxd: the Pillow filters read RGB frames, not JPEG planes");
+      p.pil = true;
+    } else if (st.ycc) {
       // JPEG planes (the host path checked ycc_plan_ok): a wave kernel or nothing
       plan_wave(im, st, b.out_dtype, p);
       if (!p.wave) return fail(MXD_ERR_UNSUPPORTED, "mxd: no wave kernel for a JPEG plane source");
@@ -249,8 +258,9 @@ int general_group(Batch& b) {
   BatchLayout& L = b.L;
   L.general_at = (int32_t)L.image_of.size();
   for (int32_t i = 0; i < b.n; i++)
-    if (!L.plans[i].band && !L.plans[i].wave) L.image_of.push_back(i);
-  if (L.general_at == b.n) return MXD_OK;
+    if (!L.plans[i].band && !L.plans[i].wave && !L.plans[i].pil) L.image_of.push_back(i);
+  const int32_t end = (int32_t)L.image_of.size();
+  if (L.general_at == end) return MXD_OK;
   // The tile kernel addresses rows from the image's row 0: a staged
   // footprint is reached through the (never dereferenced) address its
   // row 0 would have; the kernel only reads footprint rows and columns.
@@ -259,7 +269,7 @@ int general_group(Batch& b) {
     return st.base - (int64_t)st.y0 * st.stride - (int64_t)st.x0 * b.images[i].channels;
   };
   bool aligned16 = true;
-  for (int32_t k = L.general_at; k < b.n; k++) {
+  for (int32_t k = L.general_at; k < end; k++) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(base0(L.image_of[k])) | (uintptr_t)b.at(L.image_of[k]).stride;
     aligned16 = aligned16 && (a & 15) == 0;
   }
@@ -269,9 +279,9 @@ int general_group(Batch& b) {
   cfg.channels = channels;
   cfg.alpha = channels == 4 && b.images[L.image_of[L.general_at]].rgba_weighted ? 1 : 0;
   cfg.f32 = b.f32();
-  cfg.nimgs = b.n - L.general_at;
+  cfg.nimgs = end - L.general_at;
   int32_t tiles = 0;
-  for (int32_t k = L.general_at; k < b.n; k++) {
+  for (int32_t k = L.general_at; k < end; k++) {
     const int32_t i = L.image_of[k];
     const mxd_image& im = b.images[i];
     const DevTable* xt = L.plans[i].xt;
@@ -314,6 +324,56 @@ int general_group(Batch& b) {
   }
   cfg.ntiles = tiles;
   if (mxd::resample_smem_bytes(cfg) > 160 * 1024) return fail(MXD_ERR_UNSUPPORTED, "mxd: tile does not fit in LDS");
+  return MXD_OK;
+}
+
+// The images with a Pillow filter (pil_resize.hip), behind the general
+// kernel's: tiles of kPilTX columns x kPilTY rows numbered through tile_begin,
+// rows addressed from the image's row 0 like the general kernel's.
+int pil_group(Batch& b) {
+  BatchLayout& L = b.L;
+  L.pil_at = (int32_t)L.image_of.size();
+  for (int32_t i = 0; i < b.n; i++)
+    if (L.plans[i].pil) L.image_of.push_back(i);
+  if (L.pil_at == b.n) return MXD_OK;
+  mxd::PilCfg& cfg = L.pil;
+  cfg.channels = b.channels;
+  cfg.f32 = b.f32();
+  cfg.nimgs = b.n - L.pil_at;
+  int64_t tiles = 0;
+  for (int32_t k = L.pil_at; k < b.n; k++) {
+    const int32_t i = L.image_of[k];
+    const mxd_image& im = b.images[i];
+    const DevTable& xt = *L.plans[i].xt;
+    const Stored st = b.at(i);
+    ImgDev& d = L.descs[k];
+    fill(b, i, d);
+    d.src = st.base - (int64_t)st.y0 * st.stride - (int64_t)st.x0 * im.channels;
+    d.src_h = im.src_h;
+    d.src_x0 = d.src_y0 = 0;
+    d.tile_begin = (int32_t)tiles;
+    d.nstrips = (im.crop_w + mxd::kPilTX - 1) / mxd::kPilTX;
+    d.tx = mxd::kPilTX;
+    d.ty = mxd::kPilTY;
+    d.group = mxd::kPilG;
+    tiles += (int64_t)d.nstrips * ((im.crop_h + mxd::kPilTY - 1) / mxd::kPilTY);
+    // LDS bytes per source row: the widest tile footprint, the dword phase of
+    // its first byte (up to 3) and the round-up to whole dwords.
+    for (int32_t s = 0; s < d.nstrips; s++) {
+      const int32_t ox0 = s * mxd::kPilTX, ox1 = std::min(ox0 + mxd::kPilTX, im.crop_w);
+      // (vec 1: the bytes from the first tap pixel's first to the last tap pixel's last)
+      const int32_t bytes = strip_chunks(xt, im.crop_x, im.crop_w, ox0, ox1, im.flip != 0, im.channels, 1);
+      cfg.seg_bytes = std::max(cfg.seg_bytes, (bytes + 3 + 3) & ~3);
+    }
+    cfg.max_xw = std::max(cfg.max_xw, xt.width);
+    cfg.max_yw = std::max(cfg.max_yw, L.plans[i].yt->width);
+  }
+  if (tiles > INT32_MAX) return fail(MXD_ERR_UNSUPPORTED, "mxd: too many tiles in one call");
+  cfg.ntiles = (int32_t)tiles;
+  // (64 KiB: what a launch gets without asking for more; a 16 : 1 Lanczos RGB downscale on both axes takes 59)
+  if (mxd::pil_resize_smem_bytes(cfg) > 64 * 1024)
+    return fail(MXD_ERR_UNSUPPORTED, "mxd: the Pillow filters' tile does not fit in 64 KiB of LDS (" +
+                                         std::to_string(mxd::pil_resize_smem_bytes(cfg)) + " bytes)");
   return MXD_OK;
 }
 
@@ -721,6 +781,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   if (int rc = band_groups(b)) return rc;
   if (int rc = wave_groups(b)) return rc;
   if (int rc = general_group(b)) return rc;
+  if (int rc = pil_group(b)) return rc;
   append_tables(b);
   append_stages(b, callers, ops);
   if (ops.erases)
@@ -729,6 +790,7 @@ int build_layout(const LayoutEnv& env, int32_t device, const mxd_image* images, 
   for (size_t g = 0; g < L.bands.size(); g++) L.launches.push_back({4 * (int64_t)L.bands[g].units, 0, (int32_t)g});
   for (size_t g = 0; g < L.waves.size(); g++) L.launches.push_back({L.waves[g].units, 1, (int32_t)g});
   if (L.general.nimgs > 0) L.launches.push_back({L.general.ntiles, 2, -1});
+  if (L.pil.nimgs > 0) L.launches.push_back({L.pil.ntiles, 3, -1});
   std::stable_sort(L.launches.begin(), L.launches.end(),
                    [](const BatchLayout::Launch& x, const BatchLayout::Launch& y) { return x.units > y.units; });
   return MXD_OK;

@@ -234,7 +234,7 @@ int mxd_axis_taps(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t c
 
 int mxd_axis_taps_filter(int32_t in_size, int32_t out_size, int32_t crop_off, int32_t crop_len, int32_t filter,
                          int32_t max_taps, int32_t* first, int32_t* ntaps, float* weights, int32_t* taps_needed) {
-  if (filter < 0 || filter >= mxd::kFilterCount)
+  if (!mxd::filter_is_valid(filter))
     return fail(MXD_ERR_INVALID, "mxd: unknown filter " + std::to_string(filter));
   mxd::AxisTaps t;
   if (!mxd::build_axis_taps(in_size, out_size, crop_off, crop_len, &t, filter))
@@ -341,7 +341,9 @@ int mxd_describe_plan(const mxd_image* image, int32_t out_dtype, int32_t device,
   if (int rc = host_tables().get(device, image->src_w, image->resize_w, &p.xt, image->filter)) return rc;
   if (int rc = host_tables().get(device, image->src_h, image->resize_h, &p.yt, image->filter)) return rc;
   if (!(g_policy.load() & MXD_POLICY_NO_WAVE)) plan_wave(*image, whole(*image), out_dtype, p);
-  const int32_t v[8] = {p.wave ? 1 : 0, p.kind, p.bucket, p.s, p.dmax, p.q, p.nstrips, p.pp};
+  // (a Pillow filter: pil_resize_rows under every policy; plan_wave declined it)
+  const int32_t v[8] = {mxd::filter_is_pil(image->filter) ? 2 : p.wave ? 1 : 0, p.kind, p.bucket, p.s, p.dmax, p.q,
+                        p.nstrips, p.pp};
   std::memcpy(info8, v, sizeof v);
   return MXD_OK;
 }

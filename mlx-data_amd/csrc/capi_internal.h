@@ -34,6 +34,7 @@
 #include "jpeg.h"
 #include "jpegdev.h"
 #include "jpeghuff.h"
+#include "pil_resize.h"
 #include "pixmap.h"
 #include "resample.h"
 #include "taps.h"
@@ -83,9 +84,10 @@ struct DevTable {
   float* ptr = nullptr;
   int32_t width = 0;     // max taps of any output
   int32_t padded = 0;    // weights per entry in device memory (>= kMinTabWidth)
-  int32_t filter = 0;    // mxd_filter the weights were built with (0 for an identity axis)
+  int32_t filter = 0;    // mxd_filter the weights were built with (0 for an identity axis of a float filter)
   std::vector<int32_t> first, count;  // host copy for tiling decisions
   std::vector<float> w;               // host copy of the weights, `width` per output (scatter schedules)
+  bool pil() const { return mxd::filter_is_pil(filter); }  // the device weight words are int32 8.22 coefficients
 };
 
 class TableCache {
@@ -93,9 +95,12 @@ class TableCache {
   // upload = false: host copies only (ptr stays null), for planning without a device.
   explicit TableCache(bool upload = true) : upload_(upload) {}
   int get(int32_t device, int32_t in, int32_t out, const DevTable** out_tab, int32_t filter = 0) {
-    if (filter < 0 || filter >= mxd::kFilterCount)
+    if (!mxd::filter_is_valid(filter))
       return fail(MXD_ERR_INVALID, "mxd: unknown filter " + std::to_string(filter));
-    if (in == out) filter = 0;  // the identity for every filter: one table
+    // the identity for every float filter: one table (a Pillow filter keeps its
+    // own: the integer kernel reads 8.22 coefficients, never float weights)
+    const bool pil = mxd::filter_is_pil(filter);
+    if (in == out && !pil) filter = 0;
     std::lock_guard<std::mutex> lock(mu_);
     auto key = std::make_tuple(device, in, out, filter);
     auto it = map_.find(key);
@@ -113,7 +118,11 @@ class TableCache {
       float* e = &host[(size_t)i * stride];
       std::memcpy(&e[0], &taps.first[i], 4);
       std::memcpy(&e[1], &taps.count[i], 4);
-      std::memcpy(&e[2], &taps.weight[(size_t)i * taps.width], sizeof(float) * taps.width);
+      // (a Pillow filter's weight words hold the coefficients as int32)
+      if (pil)
+        std::memcpy(&e[2], &taps.coef[(size_t)i * taps.width], sizeof(int32_t) * taps.width);
+      else
+        std::memcpy(&e[2], &taps.weight[(size_t)i * taps.width], sizeof(float) * taps.width);
     }
     auto tab = std::make_unique<DevTable>();
     tab->width = taps.width;
@@ -168,6 +177,7 @@ struct ImgPlan {
   int32_t nstrips = 0, tx = 0, q = 0, shift = 0;
   int32_t pp = 0;  // source pixels per lane
   bool ycc = false;  // reads JPEG sample planes (Stored::ycc)
+  bool pil = false;  // a Pillow filter: runs on pil_resize_rows (pil_resize.hip), never on the others
 };
 
 // Shape of the scatter schedule for crop rows [off, off+len) of a vertical
@@ -345,12 +355,12 @@ struct BatchLayout {
   };
   struct Launch {
     int64_t units;  // a band unit (a workgroup) counts as 4 wave units
-    int32_t kind;   // 0 band, 1 wave, 2 general
+    int32_t kind;   // 0 band, 1 wave, 2 general, 3 pil_resize_rows
     int32_t group;
   };
   int32_t n = 0;
   std::vector<ImgPlan> plans;     // by batch index
-  std::vector<int32_t> image_of;  // batch index of descriptor k < n: band, then wave, then general images
+  std::vector<int32_t> image_of;  // batch index of descriptor k < n: band, then wave, then general, then Pillow-filter images
   // One upload, in ImgDev-sized blocks: the n descriptors, the unit -> image
   // tables from tables_at, the stages' entries from fmt_at (Stage::at each).
   // fmt_at is where the tables end, with or without stages; the second pass,
@@ -361,6 +371,10 @@ struct BatchLayout {
   std::vector<WaveGroup> waves;
   int32_t general_at = 0;  // first descriptor of the general kernel
   LaunchCfg general{};     // nimgs == 0: no general launch
+  // The images with a Pillow filter, behind the general kernel's: descriptors
+  // pil_at .. n - 1, one launch of pil_resize_rows (pil_resize.hip).
+  int32_t pil_at = 0;
+  mxd::PilCfg pil{};       // nimgs == 0: no such launch
   std::vector<Launch> launches;  // largest first
   // What follows the resize: the stage chain (the rule above PostOps), in
   // launch order.  A stage's entries lie in the upload from block `at`:

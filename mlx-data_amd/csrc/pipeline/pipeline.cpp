@@ -845,17 +845,29 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
 }  // namespace
 
 namespace {
-const char* const kFilterNames[] = {"triangle", "catmullrom", "mitchell", "cubicbspline"};
+// The names and their mxd_filter ids (not dense: Pillow's filters are 16..18).
+const struct {
+  const char* name;
+  int id;
+} kFilterNames[] = {{"triangle", MXD_FILTER_TRIANGLE},         {"catmullrom", MXD_FILTER_CATMULLROM},
+                    {"mitchell", MXD_FILTER_MITCHELL},         {"cubicbspline", MXD_FILTER_CUBICBSPLINE},
+                    {"pil_bilinear", MXD_FILTER_PIL_BILINEAR}, {"pil_bicubic", MXD_FILTER_PIL_BICUBIC},
+                    {"pil_lanczos", MXD_FILTER_PIL_LANCZOS}};
 }
 
 int parse_filter(const std::string& name) {
-  for (int f = 0; f < 4; f++)
-    if (name == kFilterNames[f]) return f;
+  for (const auto& f : kFilterNames)
+    if (name == f.name) return f.id;
   throw std::invalid_argument("image_resize: unknown filter '" + name +
-                              "' (one of triangle, catmullrom, mitchell, cubicbspline)");
+                              "' (one of triangle, catmullrom, mitchell, cubicbspline, pil_bilinear, pil_bicubic, "
+                              "pil_lanczos)");
 }
 
-const char* filter_name(int filter) { return kFilterNames[filter >= 0 && filter < 4 ? filter : 0]; }
+const char* filter_name(int filter) {
+  for (const auto& f : kFilterNames)
+    if (filter == f.id) return f.name;
+  return kFilterNames[0].name;
+}
 
 // op/ImageTransform.cpp:22-31 + core/image/ImageIO.cpp:39-49 + core/video/Video.cpp:69-79
 std::shared_ptr<Array> ImageOp::apply_key(const std::shared_ptr<Array>& x) const {

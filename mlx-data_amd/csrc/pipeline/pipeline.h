@@ -82,7 +82,8 @@ struct ImagePlan {
   // Went through core::image::resize (stbir): 4-channel images are then
   // alpha-weighted (STBIR_RGBA); crops and mirrors alone never are.
   bool resampled = false;
-  // mxd_filter of the pending resize (0 = triangle, the reference's).  One
+  // mxd_filter of the pending resize (0 = triangle, the reference's; 16..18 =
+  // Pillow's 8-bit resize).  One
   // plan holds one resize: a second one materialises the first.
   int filter = 0;
   // image_to_float: the kernel writes float32 q / 255 (MXD_F32_DIV255)
@@ -275,8 +276,10 @@ std::shared_ptr<Array> stack_frames(const std::vector<std::shared_ptr<Array>>& f
 
 // The resize ops' `filter` argument: "triangle" (the reference's, the
 // default), "catmullrom" (PIL BICUBIC / torch bicubic), "mitchell",
-// "cubicbspline" -> mxd_filter.  Any other name: std::invalid_argument
-// (Python: ValueError) naming the four.
+// "cubicbspline", and Pillow's 8-bit resize byte for byte: "pil_bilinear",
+// "pil_bicubic" (Image.resize(..., BICUBIC); "catmullrom" is its float
+// form), "pil_lanczos" -> mxd_filter.  Any other name: std::invalid_argument
+// (Python: ValueError) naming the seven.
 int parse_filter(const std::string& name);
 const char* filter_name(int filter);
 

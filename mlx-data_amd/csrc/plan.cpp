@@ -324,6 +324,7 @@ void plan_band(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan
   p.band = false;
   const int32_t f32 = out_dtype == MXD_F32_DIV255 ? 1 : 0;
   if (g_policy.load() & (MXD_POLICY_NO_BAND | kWavePolicies)) return;
+  if (p.xt->pil() || p.yt->pil()) return;  // 8.22 coefficients: pil_resize_rows' (pil_resize.hip)
   const int64_t c = im.channels, elem = f32 ? 4 : 1;
   const int64_t shift = (int64_t)(reinterpret_cast<uintptr_t>(st.base) & 3);
   const int64_t row = (int64_t)(im.src_w - st.x0) * c;
@@ -377,6 +378,7 @@ void plan_wave(const mxd_image& im, const Stored& st, int32_t out_dtype, ImgPlan
   p.wave = false;
   const int32_t f32 = out_dtype == MXD_F32_DIV255 ? 1 : 0;
   p.ycc = false;
+  if (p.xt->pil() || p.yt->pil()) return;  // 8.22 coefficients: pil_resize_rows' (pil_resize.hip)
   const bool ycc = st.ycc != nullptr;
   if (ycc) {
     // the cubic filters' kernels read RGB frames only (wave_cubic.hip): their
@@ -476,7 +478,8 @@ PlanKey plan_key(const mxd_image& im, const Stored& st) {
 }
 
 bool ycc_plan_ok(const mxd_image& im, const Stored& st, int32_t out_dtype, int32_t device) {
-  if (!st.ycc || (g_policy.load() & MXD_POLICY_NO_WAVE)) return false;
+  // (a Pillow filter's image takes the RGB-frame route, as a cubic filter's does)
+  if (!st.ycc || (g_policy.load() & MXD_POLICY_NO_WAVE) || mxd::filter_is_pil(im.filter)) return false;
   ImgPlan p;
   if (tables().get(device, im.src_w, im.resize_w, &p.xt, im.filter) != MXD_OK) return false;
   if (tables().get(device, im.src_h, im.resize_h, &p.yt, im.filter) != MXD_OK) return false;

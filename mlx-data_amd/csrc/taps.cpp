@@ -22,6 +22,9 @@
 // clamp.  out == in is the identity for every filter -- this project's rule:
 // Mitchell and B-spline would blur at scale 1, and a crop-only plan must stay
 // an exact copy.
+// The Pillow filters (kFilterPilBilinear .. kFilterPilLanczos) go through none
+// of this: pil_axis_taps restates Pillow's precompute_coeffs and
+// normalize_coeffs_8bpc, and their tables carry 8.22 coefficients.
 #include "taps.h"
 
 #include <algorithm>
@@ -213,6 +216,76 @@ std::vector<Run> downsample_runs(int32_t in, int32_t out, int32_t nbuild, float 
   return runs;
 }
 
+// Pillow's kernels (Resample.c bilinear_filter, bicubic_filter with a = -0.5,
+// lanczos_filter) and their supports.
+inline double pil_bilinear(double x) {
+  x = x < 0.0 ? -x : x;
+  return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+inline double pil_bicubic(double x) {
+  const double a = -0.5;
+  x = x < 0.0 ? -x : x;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+
+inline double pil_sinc(double x) {
+  if (x == 0.0) return 1.0;
+  x = x * M_PI;
+  return std::sin(x) / x;
+}
+
+inline double pil_lanczos(double x) { return -3.0 <= x && x < 3.0 ? pil_sinc(x) * pil_sinc(x / 3) : 0.0; }
+
+// Pillow's precompute_coeffs over the whole axis (box = (0, in)) and
+// normalize_coeffs_8bpc, for outputs [off, off + len): every step in double,
+// in Pillow's order, so the 8.22 coefficients are Pillow's bit for bit.  Taps
+// are clipped at the borders (never folded) and keep their zeros.
+void pil_axis_taps(int32_t in, int32_t out, int32_t off, int32_t len, AxisTaps* t, int32_t filter) {
+  const Kernel f = filter == kFilterPilBilinear ? pil_bilinear : filter == kFilterPilBicubic ? pil_bicubic : pil_lanczos;
+  const double sup = filter == kFilterPilBilinear ? 1.0 : filter == kFilterPilBicubic ? 2.0 : 3.0;
+  const double scale = (double)in / (double)out;
+  const double filterscale = scale < 1.0 ? 1.0 : scale;
+  const double support = sup * filterscale;
+  const int32_t ksize = (int32_t)std::ceil(support) * 2 + 1;
+  const double ss = 1.0 / filterscale;
+  std::vector<double> w((size_t)len * ksize, 0.0);
+  t->first.assign(len, 0);
+  t->count.assign(len, 0);
+  int32_t width = 1;
+  for (int32_t i = 0; i < len; i++) {
+    const double center = (off + i + 0.5) * scale;
+    int32_t xmin = (int32_t)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int32_t xmax = (int32_t)(center + support + 0.5);
+    if (xmax > in) xmax = in;
+    xmax -= xmin;
+    double* k = &w[(size_t)i * ksize];
+    double ww = 0.0;
+    for (int32_t x = 0; x < xmax; x++) {
+      k[x] = f((x + xmin - center + 0.5) * ss);
+      ww += k[x];
+    }
+    for (int32_t x = 0; x < xmax; x++)
+      if (ww != 0.0) k[x] /= ww;
+    t->first[i] = xmin;
+    t->count[i] = xmax;
+    width = std::max(width, xmax);
+  }
+  t->width = width;
+  t->coef.assign((size_t)len * width, 0);
+  t->weight.assign((size_t)len * width, 0.0f);
+  for (int32_t i = 0; i < len; i++)
+    for (int32_t x = 0; x < t->count[i]; x++) {
+      const double v = w[(size_t)i * ksize + x];
+      const int32_t c = v < 0 ? (int32_t)(-0.5 + v * (1 << kPilPrecisionBits)) : (int32_t)(0.5 + v * (1 << kPilPrecisionBits));
+      t->coef[(size_t)i * width + x] = c;
+      t->weight[(size_t)i * width + x] = (float)c / (float)(1 << kPilPrecisionBits);  // exact: |c| < 2^24
+    }
+}
+
 }  // namespace
 
 int32_t AxisTaps::lo() const {
@@ -228,12 +301,19 @@ int32_t AxisTaps::hi() const {
 }
 
 bool build_axis_taps(int32_t in, int32_t out, int32_t off, int32_t len, AxisTaps* t, int32_t filter) {
-  if (filter < 0 || filter >= kFilterCount) return false;
+  if (!filter_is_valid(filter)) return false;
   if (in <= 0 || out <= 0 || len <= 0 || off < 0 || off + len > out) return false;
   t->in_size = in;
   t->out_size = out;
   t->off = off;
   t->len = len;
+  t->coef.clear();
+  if (filter_is_pil(filter)) {
+    // (out == in included: Pillow skips that pass, and these coefficients are
+    // 2^22 at the centre and 0 elsewhere, which leaves every byte as it is)
+    pil_axis_taps(in, out, off, len, t, filter);
+    return true;
+  }
   std::vector<Run> all;
   if (in == out) {
     all.resize(out);

@@ -20,6 +20,7 @@ struct AxisTaps {
   std::vector<int32_t> first;   // [len] first input index of each output
   std::vector<int32_t> count;   // [len] taps of each output (>= 1)
   std::vector<float> weight;    // [len][width], zero padded
+  std::vector<int32_t> coef;    // Pillow filters only: [len][width] 8.22 coefficients (weight = coef / 2^22)
   int32_t lo() const;           // smallest input index touched by the window
   int32_t hi() const;           // largest input index touched by the window
 };
@@ -31,8 +32,16 @@ enum Filter : int32_t {
   kFilterCatmullRom = 1,
   kFilterMitchell = 2,
   kFilterCubicBSpline = 3,
-  kFilterCount = 4
+  kFilterCount = 4,  // the float filters are 0 .. kFilterCount - 1
+  // Pillow's 8-bit resize (Resample.c): 8.22 fixed-point coefficients, the
+  // kernel pil_resize_rows' (pil_resize.hip) and mxd_pil_resize_u8's.
+  kFilterPilBilinear = 16,
+  kFilterPilBicubic = 17,
+  kFilterPilLanczos = 18
 };
+inline bool filter_is_pil(int32_t f) { return f >= kFilterPilBilinear && f <= kFilterPilLanczos; }
+inline bool filter_is_valid(int32_t f) { return (f >= 0 && f < kFilterCount) || filter_is_pil(f); }
+constexpr int kPilPrecisionBits = 22;  // Pillow's PRECISION_BITS: 32 - 8 - 2
 
 // Builds taps for outputs [off, off+len) of an in_size -> out_size resize.
 // Returns false if the arguments (the filter included) are invalid.

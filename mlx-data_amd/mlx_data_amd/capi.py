@@ -20,12 +20,14 @@ MXD_ERR_NOMEM = 4
 MXD_U8 = 0
 MXD_F32_DIV255 = 1
 # enum mxd_filter, by the operator surface's names
-FILTERS = {"triangle": 0, "catmullrom": 1, "mitchell": 2, "cubicbspline": 3}
+FILTERS = {"triangle": 0, "catmullrom": 1, "mitchell": 2, "cubicbspline": 3,
+           "pil_bilinear": 16, "pil_bicubic": 17, "pil_lanczos": 18}  # pil_*: Pillow's 8-bit resize, byte for byte
 
 # Every symbol include/mxd_amd.h declares.
 EXPORTS = (
     "mxd_abi_version", "mxd_last_error", "mxd_device_count", "mxd_device_properties",
     "mxd_resize_smallest_side_dims", "mxd_center_crop_origin", "mxd_axis_taps", "mxd_axis_taps_filter",
+    "mxd_pil_resize_u8",
     "mxd_resize_crop_batch", "mxd_set_kernel_policy", "mxd_set_tuning", "mxd_describe_plan",
     "mxd_describe_band_plan", "mxd_copy_bandwidth",
     "mxd_set_device", "mxd_malloc_device", "mxd_free_device", "mxd_malloc_pinned", "mxd_free_pinned",
@@ -442,6 +444,20 @@ def make_warps(warps):
         for k in range(6):
             arr[i].m[k] = float(matrix[k]) if matrix is not None else 0.0
     return arr
+
+
+def pil_resize_u8(img, filter, resize_w, resize_h, crop=None, flip=False):
+    """mxd_pil_resize_u8: the CPU statement of a Pillow filter ("pil_bilinear", "pil_bicubic", "pil_lanczos" or its
+    id) on an (h, w) or (h, w, c) uint8 image (any row stride); crop: (x, y, w, h) in the resized image."""
+    a = img[:, :, None] if img.ndim == 2 else img
+    h, w, c = a.shape
+    assert a.dtype == np.uint8 and a.strides[1:] == (c, 1)
+    cx, cy, cw, ch = crop or (0, 0, resize_w, resize_h)
+    out = np.empty((ch, cw, c), np.uint8)
+    check(lib().mxd_pil_resize_u8(ctypes.c_void_p(a.ctypes.data), ctypes.c_int64(a.strides[0]), w, h, c,
+                                  int(FILTERS.get(filter, filter)), resize_w, resize_h, cx, cy, cw, ch, int(bool(flip)),
+                                  ctypes.c_void_p(out.ctypes.data), ctypes.c_int64(out.strides[0])))
+    return out.reshape(ch, cw) if img.ndim == 2 else out
 
 
 def warp_apply_u8(rgb, warp, out=None):

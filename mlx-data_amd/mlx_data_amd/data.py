@@ -55,10 +55,17 @@ arrays; bfloat16 has no NumPy type, so a host batch of it (and
 (and their ``_if`` forms) take the resampling filter of the resize:
 ``"triangle"`` (mlx-data's, the default), ``"catmullrom"`` (PIL ``BICUBIC``,
 torch ``bicubic`` with ``antialias=True``), ``"mitchell"`` or
-``"cubicbspline"``.  An unknown name raises ``ValueError`` when the op is made.
+``"cubicbspline"`` -- float32 filters, within +-1 of their integer
+counterparts -- or Pillow's 8-bit resize byte for byte: ``"pil_bilinear"``,
+``"pil_bicubic"`` (``Image.resize(size, BICUBIC)``, hence torchvision's
+``Resize`` / ``RandomResizedCrop`` on PIL images and timm's loaders) and
+``"pil_lanczos"``, for 1- and 3-channel images.  An unknown name raises
+``ValueError`` when the op is made.
 A pending image carries the filter of its one resize (a second resize
 materialises the first); a resize to the size the image already has is the
-identity for every filter.
+identity for every filter.  With a ``pil_*`` filter an
+``image_random_area_crop`` in front of the resize is Pillow's
+``im.crop(window).resize(size)``.
 
 Photometric augmentation stays in the launch too (the third addition):
 ``image_color_twist(key, brightness=1.0, contrast=1.0, saturation=1.0,

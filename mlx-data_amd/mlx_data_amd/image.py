@@ -37,7 +37,8 @@ def resize_crop(images, geoms, out_dtype="uint8", device=0, filter="triangle"):
 
     images: list of (H, W, C) uint8 arrays.
     geoms:  list of (resize_w, resize_h, crop_x, crop_y, crop_w, crop_h, flip).
-    filter: "triangle" (the reference's), "catmullrom", "mitchell" or "cubicbspline".
+    filter: "triangle" (the reference's), "catmullrom", "mitchell", "cubicbspline", or Pillow's 8-bit
+            resize byte for byte (1 or 3 channels): "pil_bilinear", "pil_bicubic", "pil_lanczos".
     Returns a list of (crop_h, crop_w, C) arrays (uint8, or float32 q/255).
     """
     if filter not in capi.FILTERS:

@@ -2,7 +2,11 @@
 process on one box.
 
   python tools/bench_filter.py [--workloads c2,c4] [--parent tools/libmxd_amd_var_parent.so]
-      [--out profiles/r08/filter_ab.jsonl]
+      [--out profiles/r08/filter_ab.jsonl] [--base triangle] [--filter catmullrom[,...]]
+
+(--base catmullrom --filter pil_bicubic,pil_bilinear,pil_lanczos is how
+profiles/r18/pil_resize_ab.jsonl was made: a and b then launch Catmull-Rom, and
+every name of --filter is a variant c of its own.)
 
 For each workload (bench.py's inputs, two alternating source/output sets
 resident in HBM) three variants are timed:
@@ -51,23 +55,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default="c2,c4")
     ap.add_argument("--parent", default="", help="the parent commit's libmxd_amd.so (variant a)")
-    ap.add_argument("--filter", default="catmullrom")
+    ap.add_argument("--filter", default="catmullrom", help="variant c: one filter name, or several with commas")
+    ap.add_argument("--base", default="triangle", help="the filter of variants a and b")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     lines = []
     for wl in args.workloads.split(","):
         capi, L, stream, sets, mode, alg, sizes, geoms, f32 = band_sweep.setup(wl)
-        fid = capi.FILTERS[args.filter]
-        cubic = [with_filter(capi, s[2], s[3], fid) for s in sets]
+        base_sets = [with_filter(capi, s[2], s[3], capi.FILTERS[args.base]) for s in sets]
         variants = {}
         if args.parent:
             P = ctypes.CDLL(os.path.abspath(args.parent), mode=os.RTLD_LOCAL | os.RTLD_NOW)
             P.mxd_last_error.restype = ctypes.c_char_p
             if P.mxd_set_device(0) != 0:
                 raise RuntimeError("parent library: mxd_set_device failed")
-            variants["a_parent_triangle"] = (P, [s[2] for s in sets])
-        variants["b_triangle"] = (L, [s[2] for s in sets])
-        variants["c_" + args.filter] = (L, cubic)
+            variants["a_parent_" + args.base] = (P, base_sets)
+        variants["b_" + args.base] = (L, base_sets)
+        for f in args.filter.split(","):
+            variants["c_" + f] = (L, [with_filter(capi, s[2], s[3], capi.FILTERS[f]) for s in sets])
         hs = ctypes.c_void_p(stream.handle)
         e0, e1 = capi.Event(), capi.Event()
 
@@ -108,12 +113,14 @@ def main():
         for name, t in times.items():
             rec[name] = {"ms_per_launch": round(statistics.median(t), 5), "min": round(min(t), 5),
                          "max": round(max(t), 5), "launches_per_window": k[name]}
-        b, c = rec["b_triangle"], rec["c_" + args.filter]
-        base = rec.get("a_parent_triangle", b)
-        rec["cubic_over_triangle"] = round(c["ms_per_launch"] / base["ms_per_launch"], 4)
-        rec["cubic_differs"] = bool(not np.array_equal(outs["b_triangle"], outs["c_" + args.filter]))
-        if "a_parent_triangle" in rec:
-            rec["b_equals_a_bytes"] = bool(np.array_equal(outs["a_parent_triangle"], outs["b_triangle"]))
+        b = rec["b_" + args.base]
+        base = rec.get("a_parent_" + args.base, b)
+        rec["base"] = args.base
+        for f in args.filter.split(","):
+            rec["c_" + f]["over_base"] = round(rec["c_" + f]["ms_per_launch"] / base["ms_per_launch"], 4)
+            rec["c_" + f]["differs"] = bool(not np.array_equal(outs["b_" + args.base], outs["c_" + f]))
+        if "a_parent_" + args.base in rec:
+            rec["b_equals_a_bytes"] = bool(np.array_equal(outs["a_parent_" + args.base], outs["b_" + args.base]))
             rec["b_inside_a_range"] = bool(base["min"] <= b["ms_per_launch"] <= base["max"])
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
