@@ -81,6 +81,8 @@ extern "C" {
  * 7, added without a new number (test for MXD_HAS_PIL_BLUR / the symbols): the
  * enhance ops MXD_ENHANCE_PIL_GAUSSIAN_BLUR and MXD_ENHANCE_PIL_BOX_BLUR and
  * mxd_pil_blur_params.
+ * 7, added without a new number (test for MXD_HAS_PIL_HUE): the enhance op
+ * MXD_ENHANCE_PIL_HUE, through the existing calls; no new symbol.
  * 7, added without a new number (test for MXD_HAS_ERASE / the symbols): Random
  * Erasing behind the output form -- mxd_erase_mode, mxd_erase_elem, mxd_erase,
  * mxd_erase_validate, mxd_erase_apply, mxd_erase_normals,
@@ -101,6 +103,7 @@ extern "C" {
 #define MXD_HAS_MIX 1
 #define MXD_HAS_GAUSSIAN_BLUR 1
 #define MXD_HAS_PIL_BLUR 1
+#define MXD_HAS_PIL_HUE 1
 #define MXD_HAS_ERASE 1
 #define MXD_HAS_PIL_RESIZE 1
 
@@ -868,6 +871,32 @@ int mxd_jpeg_resize_crop_to_device_warp(const mxd_jpeg_image* images, const mxd_
  * not.  A pass is symmetric, so these blurs commute with the mirror too.
  * mxd_pil_blur_params (below) gives fr, ww, fw and the pass count.
  *
+ * PIL_HUE is the hue part of torchvision's ColorJitter on a PIL image
+ * (adjust_hue: SimCLR, MoCo, BYOL, DINO, Barlow Twins, VICReg), bit for bit:
+ * Pillow's convert("HSV"), H += shift modulo 256, convert("RGB").  It is not
+ * mxd_color_twist_matrix's YIQ rotation: both conversions round through bytes,
+ * so even shift 0 rewrites most colours.  reserved[0] is the shift, a byte
+ * 0..255 -- for a hue_factor in -0.5..0.5, (int)(hue_factor * 255) & 255 with
+ * the product a double's, truncated toward zero: NumPy's uint8 cast --, and
+ * factor and reserved[1] are 0.  With f32(.) a rounding to float32, / of two
+ * float32 a float32 division, everything else in double and nothing fused,
+ * for the bytes r, g, b of a pixel:
+ *
+ *   V = max(r, g, b), m = min(r, g, b); V == m: H = S = 0; else
+ *   cr = f32(V - m), s = cr / f32(V), rc = f32(V - r) / cr, gc, bc likewise
+ *   h = f32(bc - gc) if r == V, else f32(2 + rc - bc) if g == V, else
+ *       f32(4 + gc - rc); x = h / 6 + 1, h = f32(x - floor(x))
+ *   H = min((int)(h 255), 255), S = min((int)(s 255), 255)
+ *   H' = (H + shift) & 255;  S == 0: the pixel is (V, V, V); else
+ *   hf = f32(H') 6 / 255, i = floor(hf), f = f32(hf - i), fs = f32(S / 255)
+ *   p = round(V (1 - fs)), q = round(V (1 - f32(fs f))) with fs f a float32
+ *   product, t = round(V (1 - fs (1 - f))); round is C's (half away from
+ *   zero), the results clipped to 0..255
+ *   (R, G, B) = (V,t,p), (q,V,p), (p,V,t), (p,q,V), (t,p,V), (V,p,q) for
+ *   i mod 6 = 0..5
+ *
+ * The op is pointwise: it commutes with the mirror and with a crop.
+ *
  * In a call the stage order is geometry, warp, enhance, tone, colour, output
  * form: the tone statistics are those of the enhanced bytes. */
 enum mxd_enhance_op {
@@ -878,14 +907,18 @@ enum mxd_enhance_op {
   /* (4 to 7 are not assigned) */
   MXD_ENHANCE_GAUSSIAN_BLUR = 8,
   MXD_ENHANCE_PIL_GAUSSIAN_BLUR = 9,
-  MXD_ENHANCE_PIL_BOX_BLUR = 10
+  MXD_ENHANCE_PIL_BOX_BLUR = 10,
+  /* (11 is not assigned) */
+  MXD_ENHANCE_PIL_HUE = 12
 };
 
 typedef struct mxd_enhance {
   int32_t op;          /* mxd_enhance_op; NONE: the image's bytes stay as they are, factor is not read */
   float factor;        /* f: finite, 0 <= f <= 1e6; GAUSSIAN_BLUR: sigma, finite, 0 < sigma <= 1e6;
-                          PIL_GAUSSIAN_BLUR, PIL_BOX_BLUR: Pillow's radius, finite, >= 0, (int)fr + 1 <= 16 */
-  int32_t reserved[2]; /* must be 0; GAUSSIAN_BLUR: reserved[0] is the kernel size k (odd, 3..33), reserved[1] 0 */
+                          PIL_GAUSSIAN_BLUR, PIL_BOX_BLUR: Pillow's radius, finite, >= 0, (int)fr + 1 <= 16;
+                          PIL_HUE: 0 */
+  int32_t reserved[2]; /* must be 0; GAUSSIAN_BLUR: reserved[0] is the kernel size k (odd, 3..33), reserved[1] 0;
+                          PIL_HUE: reserved[0] is the hue shift, 0..255, reserved[1] 0 */
 } mxd_enhance;
 
 /* Host only: the CPU statement of the arithmetic above on the w x h packed
@@ -928,7 +961,8 @@ int mxd_pil_blur_params(int32_t op, float radius, float* fr, uint32_t* ww, uint3
  * channels != 3; everything is validated before any launch.  Every image is
  * resized as a u8 image into a scratch by the kernels of the plain calls; one
  * more launch on the same stream (enhance_rows; blur_rows for the images whose
- * op is GAUSSIAN_BLUR, pilblur_rows for PIL_GAUSSIAN_BLUR and PIL_BOX_BLUR)
+ * op is GAUSSIAN_BLUR, pilblur_rows for PIL_GAUSSIAN_BLUR and PIL_BOX_BLUR,
+ * hue_rows for PIL_HUE)
  * reads those rows, or the warp
  * stage's, and writes the destinations when nothing follows, else the other
  * of the two scratches, which the row stage of the _tone calls reads. */

@@ -447,6 +447,11 @@ int launch_stage(const BatchLayout& L, const BatchLayout::Stage& st, const ImgDe
                                reinterpret_cast<const mxd::PilBlurRecDev*>(dev + L.pilblur_at), L.pilblur_count,
                                L.pilblur_units, stream);
     }
+    if (rc == 0 && L.hue_count > 0) {
+      what = "hue launch failed: ";
+      rc = mxd::launch_hue(static_cast<const mxd::EnhanceRowDev*>(entries),
+                           reinterpret_cast<const mxd::HueRecDev*>(dev + L.hue_at), L.hue_count, L.hue_units, stream);
+    }
   } else if (st.kind == StageKind::Mix) {
     what = "mix launch failed: ";
     rc = mxd::launch_mix(static_cast<const mxd::MixRowDev*>(entries), st.count, st.blocks, ofd, stream);

@@ -494,11 +494,13 @@ void fill_enhances(Batch& b, BatchLayout::Stage& st, const PostOps& ops) {
     // its box radius is 0: that one leaves the bytes as they are, like NONE.
     const bool pil = pil_blur_op(en.op);
     const bool copies = pil && pil_blur_params(en.op, en.factor).fr == 0.0f;
-    if (en.op != MXD_ENHANCE_GAUSSIAN_BLUR && (!pil || copies))
+    // A hue shift is hue_rows' (append_hues), again by the same rule.
+    if (en.op != MXD_ENHANCE_GAUSSIAN_BLUR && en.op != MXD_ENHANCE_PIL_HUE && (!pil || copies))
       st.blocks += e.tiles_x * ((im.crop_h + mxd::kEnhTileH - 1) / mxd::kEnhTileH);
     e.op = copies ? (int32_t)MXD_ENHANCE_NONE : en.op;
     // (MXD_ENHANCE_NONE reads no factor: zero, so equal calls make equal bytes)
-    e.factor = e.op == MXD_ENHANCE_NONE ? 0.0f : en.factor;
+    // (nor does MXD_ENHANCE_PIL_HUE: its shift travels in its record)
+    e.factor = e.op == MXD_ENHANCE_NONE || e.op == MXD_ENHANCE_PIL_HUE ? 0.0f : en.factor;
   }
 }
 
@@ -562,6 +564,29 @@ void append_pilblurs(Batch& b, const PostOps& ops) {
   L.pilblur_count = (int32_t)recs.size();
   L.descs.resize(L.pilblur_at + (recs.size() * sizeof(mxd::PilBlurRecDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
   std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.pilblur_at), recs.data(), recs.size() * sizeof(mxd::PilBlurRecDev));
+}
+
+// The hue table, behind the Pillow blur table and only when some image has
+// MXD_ENHANCE_PIL_HUE: one record per such image, in batch order.  The shift is
+// part of the upload's bytes.
+void append_hues(Batch& b, const PostOps& ops) {
+  BatchLayout& L = b.L;
+  std::vector<mxd::HueRecDev> recs;
+  for (int32_t i = 0; i < b.n; i++) {
+    const mxd_enhance& en = ops.enhances[i];
+    if (en.op != MXD_ENHANCE_PIL_HUE) continue;
+    mxd::HueRecDev r{};
+    r.entry = i;
+    r.unit_begin = L.hue_units;
+    r.shift = en.reserved[0];
+    L.hue_units += (L.images[i].crop_h + mxd::kHueRows - 1) / mxd::kHueRows;
+    recs.push_back(r);
+  }
+  if (recs.empty()) return;
+  L.hue_at = L.descs.size();
+  L.hue_count = (int32_t)recs.size();
+  L.descs.resize(L.hue_at + (recs.size() * sizeof(mxd::HueRecDev) + sizeof(ImgDev) - 1) / sizeof(ImgDev));
+  std::memcpy(reinterpret_cast<void*>(L.descs.data() + L.hue_at), recs.data(), recs.size() * sizeof(mxd::HueRecDev));
 }
 
 // The erase table, behind everything else of the upload and only when some
@@ -719,6 +744,7 @@ void append_stages(Batch& b, const mxd_image* callers, const PostOps& ops) {
   }
   if (ops.enhances) append_blurs(b, ops);
   if (ops.enhances) append_pilblurs(b, ops);
+  if (ops.enhances) append_hues(b, ops);
 }
 
 }  // namespace

@@ -435,6 +435,10 @@ struct BatchLayout {
   // the images whose op is PIL_GAUSSIAN_BLUR or PIL_BOX_BLUR.
   size_t pilblur_at = 0;
   int32_t pilblur_count = 0, pilblur_units = 0;
+  // The hue table (hue.hip), likewise: behind the Pillow blur table, for the
+  // images whose op is PIL_HUE.
+  size_t hue_at = 0;
+  int32_t hue_count = 0, hue_units = 0;
   // The erase table (erase.hip): erase_count records (one per non-empty box)
   // from block erase_at, behind every stage's entries and the blur table, for
   // erase_units workgroups writing erase_elem (mxd_erase_elem) elements, CHW or

@@ -4,8 +4,9 @@
 // Pillow's ImageEnhance.Sharpness / Color / Brightness, bit for bit, and for
 // GAUSSIAN_BLUR a separable Gaussian with torchvision's kernel and reflect
 // padding, and for PIL_GAUSSIAN_BLUR / PIL_BOX_BLUR Pillow's fixed-point box
-// passes.  The device side is enhance.hip, blur.hip and
-// pilblur.hip; the two sides share no code.
+// passes, and for PIL_HUE Pillow's RGB -> HSV -> RGB round trip with the hue
+// shifted.  The device side is enhance.hip, blur.hip,
+// pilblur.hip and hue.hip; the two sides share no code.
 // Host only.
 #include "capi_internal.h"
 
@@ -38,6 +39,12 @@ int enhance_check(const mxd_enhance& e, int32_t i) {
     if (!(std::isfinite(e.factor) && e.factor >= 0.0f)) return at("factor (the radius) must be finite and not negative");
     if (!(pil_blur_params(e.op, e.factor).fr < (float)mxd::kBlurMaxR))
       return at("factor (the radius) is too large: its box radius must stay below " + std::to_string(mxd::kBlurMaxR));
+    return MXD_OK;
+  }
+  if (e.op == MXD_ENHANCE_PIL_HUE) {
+    if (e.reserved[0] < 0 || e.reserved[0] > 255) return at("hue shift must be in 0..255");
+    if (e.reserved[1] != 0) return at("reserved must be 0");
+    if (!(e.factor == 0.0f)) return at("factor must be 0");
     return MXD_OK;
   }
   if (e.op < MXD_ENHANCE_NONE || e.op > MXD_ENHANCE_BRIGHTNESS) return at("unknown op " + std::to_string(e.op));
@@ -129,6 +136,51 @@ void pil_blur(const uint8_t* rgb, int w, int h, int64_t stride, const PilBlurPar
     a.swap(b);
   }
   for (int y = 0; y < h; y++) std::memcpy(out + (int64_t)y * out_stride, &a[(size_t)y * n], n);
+}
+
+// PIL_HUE (mxd_amd.h) of one pixel: Pillow's rgb2hsv, the shift of H modulo
+// 256, Pillow's hsv2rgb.  A float is a float32 and a double a float64; every
+// operation is rounded where it stands.
+inline void pil_hue(const uint8_t* q, int shift, uint8_t* o) {
+  const int r = q[0], g = q[1], b = q[2];
+  const int maxc = std::max(r, std::max(g, b)), minc = std::min(r, std::min(g, b));
+  int H = 0, S = 0;
+  if (maxc != minc) {
+    const float cr = (float)(maxc - minc);
+    const float s = cr / (float)maxc;
+    const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
+    float h;
+    if (r == maxc) h = bc - gc;
+    else if (g == maxc) h = (float)(2.0 + (double)rc - (double)bc);
+    else h = (float)(4.0 + (double)gc - (double)rc);
+    h = (float)std::fmod((double)h / 6.0 + 1.0, 1.0);
+    H = std::min(std::max((int)((double)h * 255.0), 0), 255);
+    S = std::min(std::max((int)((double)s * 255.0), 0), 255);
+  }
+  H = (H + shift) & 255;
+  if (S == 0) {
+    o[0] = o[1] = o[2] = (uint8_t)maxc;
+    return;
+  }
+  const double hf = (double)(float)H * 6.0 / 255.0;
+  const double fl = std::floor(hf);
+  const float f = (float)(hf - fl);
+  const float fs = (float)((double)S / 255.0);
+  const float fsf = fs * f;
+  const double V = (double)maxc;
+  auto byte = [](double x) { return (uint8_t)std::min(std::max(std::round(x), 0.0), 255.0); };
+  const uint8_t v = (uint8_t)maxc;
+  const uint8_t p = byte(V * (1.0 - (double)fs));
+  const uint8_t qq = byte(V * (1.0 - (double)fsf));
+  const uint8_t t = byte(V * (1.0 - (double)fs * (1.0 - (double)f)));
+  switch ((int)fl % 6) {
+    case 0: o[0] = v, o[1] = t, o[2] = p; break;
+    case 1: o[0] = qq, o[1] = v, o[2] = p; break;
+    case 2: o[0] = p, o[1] = v, o[2] = t; break;
+    case 3: o[0] = p, o[1] = qq, o[2] = v; break;
+    case 4: o[0] = t, o[1] = p, o[2] = v; break;
+    default: o[0] = v, o[1] = p, o[2] = qq; break;
+  }
 }
 
 }  // namespace
@@ -254,6 +306,8 @@ extern "C" int mxd_enhance_apply_u8(const uint8_t* rgb, int32_t w, int32_t h, in
       uint8_t* o = dst(y, x);
       if (op == MXD_ENHANCE_NONE) {
         std::memcpy(o, q, 3);
+      } else if (op == MXD_ENHANCE_PIL_HUE) {
+        pil_hue(q, enh->reserved[0], o);
       } else if (op == MXD_ENHANCE_BRIGHTNESS) {
         for (int c = 0; c < 3; c++) o[c] = blend(0, q[c], f);
       } else if (op == MXD_ENHANCE_COLOR) {

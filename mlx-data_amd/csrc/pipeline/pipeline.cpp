@@ -830,8 +830,9 @@ std::shared_ptr<Array> plan_crop(const std::shared_ptr<Array>& img, int64_t x, i
     return out;
   }
   ImagePlan p = geometry_view(img);
-  if ((p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) || (p.enhanced && (p.enhance_op == MXD_ENHANCE_SHARPNESS || p.enhance_op >= MXD_ENHANCE_GAUSSIAN_BLUR))) {
+  if ((p.toned && p.tone_op >= MXD_TONE_AUTOCONTRAST) || (p.enhanced && (p.enhance_op == MXD_ENHANCE_SHARPNESS || (p.enhance_op >= MXD_ENHANCE_GAUSSIAN_BLUR && p.enhance_op != MXD_ENHANCE_PIL_HUE)))) {
     // the op's statistics (SHARPNESS: copied ring; GAUSSIAN_BLUR: reflected edges; the PIL blurs: clamped edges) are those of the window it saw: run it, crop its bytes
+    // (PIL_HUE is pointwise, like COLOR and BRIGHTNESS: the crop composes)
     img->data();
     p = view(img);
   }
@@ -1380,6 +1381,7 @@ const char* enhance_name(int32_t op) {
   if (op == MXD_ENHANCE_GAUSSIAN_BLUR) return "gaussian_blur";
   if (op == MXD_ENHANCE_PIL_GAUSSIAN_BLUR) return "pil_gaussian_blur";
   if (op == MXD_ENHANCE_PIL_BOX_BLUR) return "pil_box_blur";
+  if (op == MXD_ENHANCE_PIL_HUE) return "pil_hue";
   return op >= 0 && op <= MXD_ENHANCE_BRIGHTNESS ? names[op] : "none";
 }
 
@@ -1387,10 +1389,29 @@ std::string ImageEnhance::name() const { return std::string(random_ ? "image_ran
 
 namespace {
 bool enhance_factor_ok(double f) { return std::isfinite(f) && f >= 0.0 && f <= 1e6; }
+// A double as Python's repr writes it (torchvision's message formats hue_factor so).
+std::string py_repr(double v) {
+  if (std::isnan(v)) return "nan";
+  if (std::isinf(v)) return v < 0 ? "-inf" : "inf";
+  char buf[40];
+  int prec = 1;
+  do std::snprintf(buf, sizeof buf, "%.*g", prec, v);  // the shortest digits that read back as v
+  while (std::strtod(buf, nullptr) != v && ++prec <= 17);
+  std::string s(buf);
+  if (s.find_first_of(".e") == std::string::npos) s += ".0";
+  return s;
+}
 }  // namespace
 
 // A blur's sigma or radius is checked as the float32 the launch takes.
 void ImageEnhance::check_args(const char* what) const {
+  if (op_ == MXD_ENHANCE_PIL_HUE) {
+    // torchvision's adjust_hue refuses it with these words
+    for (double f : {lo_, hi_})
+      if (!(std::isfinite(f) && f >= -0.5 && f <= 0.5))
+        throw std::invalid_argument("hue_factor (" + py_repr(f) + ") is not in [-0.5, 0.5].");
+    return;
+  }
   if (op_ == MXD_ENHANCE_PIL_GAUSSIAN_BLUR || op_ == MXD_ENHANCE_PIL_BOX_BLUR) {
     // (the box radius grows with the radius: the two ends of a range speak for what lies between)
     for (double r : {lo_, hi_})
@@ -1421,7 +1442,7 @@ ImageEnhance::ImageEnhance(std::string ikey, int32_t op, std::pair<double, doubl
       ksize_(ksize) {
   check_args(" range");
   if (lo_ > hi_)
-    throw std::invalid_argument(name() + (op_ == MXD_ENHANCE_GAUSSIAN_BLUR ? ": sigma" : op_ >= MXD_ENHANCE_PIL_GAUSSIAN_BLUR ? ": radius" : ": factor") +
+    throw std::invalid_argument(name() + (op_ == MXD_ENHANCE_GAUSSIAN_BLUR ? ": sigma" : op_ == MXD_ENHANCE_PIL_HUE ? ": hue" : op_ >= MXD_ENHANCE_PIL_GAUSSIAN_BLUR ? ": radius" : ": factor") +
                                 " range has lo > hi");
 }
 
@@ -1444,6 +1465,11 @@ std::shared_ptr<Array> ImageEnhance::mark(const std::shared_ptr<Array>& img, dou
   p.enhance_op = op_;
   p.enhance_factor = (float)factor;
   p.enhance_ksize = ksize_;
+  if (op_ == MXD_ENHANCE_PIL_HUE) {
+    // torchvision's np.array(hue_factor * 255).astype("uint8"): the double product, truncated toward zero, wrapped
+    p.enhance_factor = 0.0f;
+    p.enhance_ksize = (int32_t)(factor * 255.0) & 0xff;
+  }
   return make(p);
 }
 

@@ -137,10 +137,12 @@ struct ImagePlan {
   // image_pil_gaussian_blur, its random form and image_pil_box_blur are
   // MXD_ENHANCE_PIL_GAUSSIAN_BLUR / PIL_BOX_BLUR (enhance_factor: Pillow's
   // radius) with the same rules: a box pass is symmetric, its edges clamp.
+  // image_pil_hue and its random form are MXD_ENHANCE_PIL_HUE (enhance_factor
+  // 0; enhance_ksize: the hue shift, a byte) with COLOR's rules: pointwise.
   bool enhanced = false;
   int32_t enhance_op = 0;
   float enhance_factor = 1.0f;
-  int32_t enhance_ksize = 0;  // GAUSSIAN_BLUR only
+  int32_t enhance_ksize = 0;  // mxd_enhance::reserved[0]: GAUSSIAN_BLUR's kernel size, PIL_HUE's shift
   // image_random_erasing: the launch fills erase.box[0..count) of the output
   // elements last, behind the output form (mxd_erase: Random Erasing).  It is
   // the one image op accepted on a plan already marked f32 / formatted, since
@@ -485,6 +487,10 @@ std::array<double, 6> affine_rotate_matrix(int64_t w, int64_t h, double angle);
 // MXD_ENHANCE_PIL_BOX_BLUR (image_pil_box_blur) are Pillow's
 // ImageFilter.GaussianBlur / BoxBlur: factor is the radius, as
 // mxd_pil_blur_params accepts it.
+// MXD_ENHANCE_PIL_HUE (image_pil_hue) is torchvision's adjust_hue on a PIL
+// image: factor is hue_factor, finite and in -0.5..0.5 ("hue_factor (X) is not
+// in [-0.5, 0.5]." otherwise, torchvision's words); the plan carries the byte
+// (int)(hue_factor * 255) & 255.
 class ImageEnhance : public ImageOp {
  public:
   // op: mxd_enhance_op (not NONE); factor: finite, 0 <= factor <= 1e6.
@@ -505,7 +511,7 @@ class ImageEnhance : public ImageOp {
   double lo_, hi_;
   int32_t ksize_;
 };
-// "sharpness", "color", "brightness", "gaussian_blur", "pil_gaussian_blur", "pil_box_blur" of an mxd_enhance_op (the op is image_<name>).
+// "sharpness", "color", "brightness", "gaussian_blur", "pil_gaussian_blur", "pil_box_blur", "pil_hue" of an mxd_enhance_op (the op is image_<name>).
 const char* enhance_name(int32_t op);
 
 // op/ImageTransform.h:139-152 ImageRotate: nearest-pixel rotation about the

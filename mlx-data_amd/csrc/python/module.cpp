@@ -702,6 +702,24 @@ void dataset_ops(py::class_<D, std::shared_ptr<D>>& cls, Wrap wrap) {
           },
           py::arg("key"), py::arg("radius"), py::arg("output_key") = "")
       .def(
+          "image_pil_hue",
+          [wrap](const Self& self, const std::string& key, double hue_factor, const std::string& output_key) {
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_PIL_HUE, hue_factor, output_key));
+          },
+          py::arg("key"), py::arg("hue_factor"), py::arg("output_key") = "")
+      .def(
+          "image_random_pil_hue",
+          [wrap](const Self& self, const std::string& key, const py::object& hue, const std::string& output_key) {
+            std::pair<double, double> range;
+            try {
+              range = hue.cast<std::pair<double, double>>();
+            } catch (const py::cast_error&) {
+              throw std::invalid_argument("image_random_pil_hue: hue must be a (lo, hi) pair");
+            }
+            return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_PIL_HUE, range, output_key));
+          },
+          py::arg("key"), py::arg("hue") = py::make_tuple(-0.1, 0.1), py::arg("output_key") = "")
+      .def(
           "image_color",
           [wrap](const Self& self, const std::string& key, double factor, const std::string& output_key) {
             return wrap(self, std::make_shared<ImageEnhance>(key, MXD_ENHANCE_COLOR, factor, output_key));
@@ -1051,8 +1069,8 @@ PYBIND11_MODULE(_pipeline, m) {
     } else {
       d["warp"] = py::none();
     }
-    // the enhance op: (name, factor); a blur: ("gaussian_blur", sigma, kernel size)
-    if (p.enhanced && p.enhance_op == MXD_ENHANCE_GAUSSIAN_BLUR)
+    // the enhance op: (name, factor); a blur: ("gaussian_blur", sigma, kernel size); a hue shift: ("pil_hue", 0.0, shift byte)
+    if (p.enhanced && (p.enhance_op == MXD_ENHANCE_GAUSSIAN_BLUR || p.enhance_op == MXD_ENHANCE_PIL_HUE))
       d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor), p.enhance_ksize);
     else if (p.enhanced) d["enhance"] = py::make_tuple(enhance_name(p.enhance_op), py::float_(p.enhance_factor));
     else d["enhance"] = py::none();

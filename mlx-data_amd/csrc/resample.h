@@ -273,7 +273,7 @@ int launch_warp_cubic(const WarpRowDev* rows, int nimgs, int tile_first, int til
 constexpr int kEnhTileW = 64, kEnhTileH = 16;
 // mxd_enhance_op's values.
 enum EnhanceOp : int32_t { kEnhNone = 0, kEnhSharpness = 1, kEnhColor = 2, kEnhBrightness = 3, kEnhGaussianBlur = 8,
-                           kEnhPilGaussianBlur = 9, kEnhPilBoxBlur = 10 };
+                           kEnhPilGaussianBlur = 9, kEnhPilBoxBlur = 10, kEnhPilHue = 12 };
 struct EnhanceRowDev {
   const uint8_t* src;  // u8 rows (16-byte aligned base, stride a multiple of 16)
   uint8_t* dst;        // scratch rows like src, or the caller's u8 destination (any alignment)
@@ -324,6 +324,21 @@ struct PilBlurRecDev {
 };
 static_assert(sizeof(PilBlurRecDev) == 32, "PilBlurRecDev layout");
 int launch_pilblur(const EnhanceRowDev* rows, const PilBlurRecDev* recs, int nrecs, int nunits, void* stream);
+// Pillow's HSV hue shift of the enhance stage (hue.hip): the images whose op is
+// kEnhPilHue have no tile in enhance_rows either and one record in a table
+// behind the Pillow blur table.  The op is pointwise: hue_rows takes kHueRows
+// whole rows of one image per workgroup, units numbered through unit_begin,
+// and reads the image's rows from its enhance entry.  The shift is part of the
+// uploaded bytes.
+constexpr int kHueRows = 8;
+struct HueRecDev {
+  int32_t entry;       // the image's entry among the enhance stage's
+  int32_t unit_begin;  // first of the image's workgroups among the launch's
+  int32_t shift;       // mxd_enhance::reserved[0]: 0..255, added to H modulo 256
+  int32_t pad;
+};
+static_assert(sizeof(HueRecDev) == 16, "HueRecDev layout");
+int launch_hue(const EnhanceRowDev* rows, const HueRecDev* recs, int nrecs, int nunits, void* stream);
 // The mix stage (mix.hip): the last stage of a mix call (mxd_mix), over u8 RGB
 // scratch rows.  One entry per image; a workgroup takes kMixRows rows of one
 // image, workgroups numbered through blk_begin.  It reads the image's rows

@@ -495,6 +495,7 @@ MXD_ENHANCE_BRIGHTNESS = 3
 MXD_ENHANCE_GAUSSIAN_BLUR = 8  # factor: sigma; a third tuple member: the kernel size
 MXD_ENHANCE_PIL_GAUSSIAN_BLUR = 9  # factor: the radius of Pillow's ImageFilter.GaussianBlur
 MXD_ENHANCE_PIL_BOX_BLUR = 10  # factor: the radius of Pillow's ImageFilter.BoxBlur
+MXD_ENHANCE_PIL_HUE = 12  # factor: 0; a third tuple member: the hue shift, a byte 0..255
 
 
 class MxdEnhance(ctypes.Structure):
@@ -505,7 +506,8 @@ class MxdEnhance(ctypes.Structure):
 
 def make_enhances(enhances):
     """(op, factor) tuples -- (MXD_ENHANCE_GAUSSIAN_BLUR, sigma, kernel_size) for a blur,
-    (MXD_ENHANCE_PIL_GAUSSIAN_BLUR, radius) or (MXD_ENHANCE_PIL_BOX_BLUR, radius) for Pillow's --
+    (MXD_ENHANCE_PIL_GAUSSIAN_BLUR, radius) or (MXD_ENHANCE_PIL_BOX_BLUR, radius) for Pillow's,
+    (MXD_ENHANCE_PIL_HUE, 0.0, shift) for Pillow's HSV hue shift --
     (or MxdEnhance values) -> ctypes array of mxd_enhance."""
     arr = (MxdEnhance * max(1, len(enhances)))()
     for i, e in enumerate(enhances):

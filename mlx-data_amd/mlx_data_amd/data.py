@@ -170,6 +170,19 @@ and at most about 16.4 (Gaussian) or below 16 (box); radius 0 leaves the image
 as it is; the random form draws one uniform radius per image (a video draws
 once).  They compose exactly as ``image_gaussian_blur`` does.
 
+``image_pil_hue(key, hue_factor)`` and
+``image_random_pil_hue(key, hue=(lo, hi))`` are the hue part of torchvision's
+``ColorJitter`` on a PIL image (``adjust_hue``: Pillow's ``convert("HSV")``, the
+byte ``int(hue_factor * 255) & 255`` added to H modulo 256, ``convert("RGB")``),
+byte for byte -- not the YIQ rotation of ``image_color_twist(hue=)``.
+``hue_factor`` is finite and in -0.5..0.5 (``ValueError`` with torchvision's
+words otherwise); the random form draws one uniform ``hue_factor`` per image (a
+video draws once).  With ``image_brightness``, ``image_contrast`` and
+``image_color`` this completes a Pillow-exact ColorJitter.  The op is pointwise
+and composes as ``image_color`` does: a flip, a crop, tone and colour ops and
+the output forms after it; a resize, ``image_rotate``, warp or second enhance
+op materialises what is pending.
+
 ``image_random_erasing(key, prob=0.5, area=(0.02, 1/3), aspect=(0.3, 1/0.3),
 mode="const" | "rand" | "pixel", count=1 | (lo, hi), value=0.0,
 output_key="")`` (with ``image_random_erasing_if``) is timm's ``RandomErasing``
@@ -258,7 +271,7 @@ def _add_if_variants(cls):
                  "image_sharpness", "image_color", "image_brightness", "image_random_sharpness",
                  "image_random_color", "image_random_brightness", "image_gaussian_blur",
                  "image_random_gaussian_blur", "image_pil_gaussian_blur", "image_random_pil_gaussian_blur",
-                 "image_pil_box_blur", "image_random_erasing"):
+                 "image_pil_box_blur", "image_pil_hue", "image_random_pil_hue", "image_random_erasing"):
         def op_if(self, cond, *args, _name=name, **kwargs):
             return getattr(self, _name)(*args, **kwargs) if cond else self
 

@@ -45,6 +45,17 @@ process for --rounds rounds (3 rounds: 9 windows each):
           normalise, permute and cast to bfloat16
   a, a2, n as above
 
+--op hue times Pillow's HSV hue shift:
+
+  h       mxd_resize_crop_batch_enhance, MXD_ENHANCE_PIL_HUE with shift 25 for
+          every image (hue_rows), the same format
+  r       MXD_ENHANCE_BRIGHTNESS 1.5 on the same images: the pointwise path of
+          enhance_rows, the same bytes moved -- the yardstick for h
+  d       the u8 mxd_resize_crop_batch, then torch on the same stream: the two
+          conversions as elementwise float32 / float64 ops (torch_pil_hue),
+          / 255, normalise, permute and cast to bfloat16
+  a, a2, n as above
+
 --variants picks a subset (a profiler run of the enhance call alone: --variants b).
 --lib times another build of the library: enhance.hip compiled with
 -DMXD_ENH_LDS stages the tile and its halo in LDS instead of reading the
@@ -90,6 +101,38 @@ def torch_pil_blur(torch, x, R, ww, fw, passes):
             t = ((box.long() * ww + far.long() * fw + (1 << 23)) >> 24).float()
             x = t if axis == 3 else t.transpose(2, 3)
     return x
+
+
+HUE_SHIFT = 25
+
+
+def torch_pil_hue(torch, u8, shift):
+    """MXD_ENHANCE_PIL_HUE's statement (include/mxd_amd.h) on a (..., 3) uint8 tensor:
+    every operation at the statement's precision; returns float64 byte values."""
+    x = u8.int()
+    r, g, b = x.unbind(-1)
+    maxc, minc = x.amax(-1), x.amin(-1)
+    grey = maxc == minc
+    cr = torch.where(grey, 1, maxc - minc).float()
+    s = (maxc - minc).float() / torch.where(grey, 1, maxc).float()
+    rc, gc, bc = ((maxc - c).float() / cr for c in (r, g, b))
+    h = torch.where(r == maxc, (bc - gc).double(),
+                    torch.where(g == maxc, 2.0 + rc.double() - bc.double(), 4.0 + gc.double() - rc.double())).float()
+    xh = h.double() / 6.0 + 1.0
+    h = (xh - xh.floor()).float()
+    H = (h.double() * 255.0).int().clamp(max=255)
+    S = (s.double() * 255.0).int().clamp(max=255)
+    hf = ((H + shift) & 255).float().double() * 6.0 / 255.0
+    i = hf.floor()
+    f = (hf - i).float()
+    fs = (S.double() / 255.0).float()
+    V = maxc.double()
+    p = torch.floor(V * (1.0 - fs.double()) + 0.5)  # (C's round of a value that is never negative)
+    q = torch.floor(V * (1.0 - (fs * f).double()) + 0.5)
+    t = torch.floor(V * (1.0 - fs.double() * (1.0 - f.double())) + 0.5)
+    pick = torch.tensor([[0, 1, 2], [3, 0, 2], [2, 0, 1], [2, 3, 0], [1, 2, 0], [0, 2, 3]], device=u8.device)  # of V, t, p, q
+    out = torch.gather(torch.stack([V, t, p, q], -1), -1, pick[i.long() % 6]).clamp(0, 255)
+    return torch.where((S == 0).unsqueeze(-1), V.unsqueeze(-1), out)
 
 
 def run_workload(name, capi, torch, rounds, emit, only, op="sharpness", blur_shapes=()):
@@ -185,6 +228,16 @@ def run_workload(name, capi, torch, rounds, emit, only, op="sharpness", blur_sha
                  "p16": enhance_call(capi.make_enhances([(gauss, PIL_RADIUS_WIDE)] * B)),
                  "g": enhance_call(capi.make_enhances([(capi.MXD_ENHANCE_GAUSSIAN_BLUR, BLUR_SIGMA, BLUR_K)] * B)),
                  "n": enhance_call(none), "d": d_pil, "a2": a}
+    if op == "hue":
+        def d_hue(i):
+            call(L.mxd_resize_crop_batch(arrays["u8"][i % 2], B, capi.MXD_U8, dev, hs))
+            with torch.cuda.stream(ext):
+                y = torch_pil_hue(torch, u8s[i % 2], HUE_SHIFT).float().permute(0, 3, 1, 2)
+                ((y / 255 - mean_t) / std_t).to(torch.bfloat16)
+
+        every = {"a": a, "h": enhance_call(capi.make_enhances([(capi.MXD_ENHANCE_PIL_HUE, 0.0, HUE_SHIFT)] * B)),
+                 "r": enhance_call(capi.make_enhances([(capi.MXD_ENHANCE_BRIGHTNESS, FACTOR)] * B)),
+                 "n": enhance_call(none), "d": d_hue, "a2": a}
     variants = {k: f for k, f in every.items() if not only or k in only}
     try:
         for f in variants.values():  # every shape and variant warmed first
@@ -200,7 +253,13 @@ def run_workload(name, capi, torch, rounds, emit, only, op="sharpness", blur_sha
             med[k] = statistics.median(w)
             emit({"workload": name, "variant": k, "images": B, "ms_per_launch": round(med[k], 5), "min": min(w),
                   "max": max(w), "windows": w})
-        if not only and op == "pilblur":
+        if not only and op == "hue":
+            lo = min(med["a"], med["a2"])
+            emit({"workload": name, "summary": True, "op": "pil_hue", "shift": HUE_SHIFT,
+                  "h_over_a": round(med["h"] / lo, 4), "r_over_a": round(med["r"] / lo, 4), "n_over_a": round(med["n"] / lo, 4),
+                  "h_over_r": round(med["h"] / med["r"], 4), "d_over_h": round(med["d"] / med["h"], 2),
+                  "a_spread": round(abs(med["a"] - med["a2"]) / lo, 4)})
+        elif not only and op == "pilblur":
             lo = min(med["a"], med["a2"])
             emit({"workload": name, "summary": True, "op": "pil_gaussian_blur", "radius": PIL_RADIUS,
                   "p_over_a": round(med["p"] / lo, 4), "n_over_a": round(med["n"] / lo, 4),
@@ -231,7 +290,7 @@ def main():
     ap.add_argument("--workloads", default="c2,c4")
     ap.add_argument("--variants", default="")
     ap.add_argument("--out", default="")
-    ap.add_argument("--op", default="sharpness", choices=("sharpness", "blur", "pilblur"))
+    ap.add_argument("--op", default="sharpness", choices=("sharpness", "blur", "pilblur", "hue"))
     ap.add_argument("--blur-shapes", default="", help="--op blur: segment rows : rows per step, e.g. 32:8,112:8,56:4")
     ap.add_argument("--lib", default="", help="another build of libmxd_amd.so to time (a compile-time variant)")
     args = ap.parse_args()
